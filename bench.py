@@ -14,18 +14,25 @@ HBM and alternate, so the decode stages of step i+1 run beside the integrate ker
 step is still one complete pipeline pass over 10,000 documents; all K steps are complete when the timed region closes.
 `--inflight 1` runs them strictly one after the other.
 
-    python bench.py                       # N=1
+    python bench.py                       # N=1: set-up, warm-up, the timed steps, one JSON line
+    python bench.py --full                # ... and every other leg described below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-The JSON line carries, beside the contract fields: `roofline` (dominant kernel: algorithmic bytes per launch over its
+A plain run does what the headline figure needs and nothing else: it builds and stages the documents, warms up, times the K
+steps and prints the line (`metric`, `value`, `unit`, `ms_per_step`, ..., `config`, and the HIP-event averages of the timed
+steps, which cost no run of their own).  `--dump-outputs DIR` also writes what the last timed step returned (dump_outputs).
+
+With `--full` the JSON line carries, beside those fields: `parity` (every document of the timed batch against the oracle),
+`roofline` (dominant kernel: algorithmic bytes per launch over its
 HIP-event duration in the timed region and alone; `traffic` from the committed rocprofv3 --pmc passes, named in
 `traffic_source`), `cpu_baseline` (the oracle — a CPU restatement of the reference path, kind "port" — as one
 single-threaded process per core the container's cgroup grants, with the 1-core and half-cores points), and at N=1:
 `end_to_end` (every step stages the blobs from host memory and fetches JSON + VV back: PCIe-inclusive) and
 `other_configs` (BASELINE configs[0], [2], [3], [4], a heterogeneous configs[1] batch and — not a BASELINE config, guarded —
 a MovableList batch for SURVEY §8f N4, each checked against the
-oracle before it is timed).  `--no-cpu-baseline --no-end-to-end --no-other-configs` leaves the timed steps only.
+oracle before it is timed).  `--full --no-cpu-baseline --no-end-to-end --no-other-configs` leaves the timed steps, the parity
+check and the two serialized passes of the roofline.
 """
 import argparse
 import json
@@ -695,85 +702,53 @@ def resident_configs(device, cores, n_docs=10000, full=True):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--docs", type=int, default=10000, help="documents per GPU (configs[1]: 10,000)")
-    ap.add_argument("--base-ops", type=int, default=50000)
-    ap.add_argument("--branch-ops", type=int, default=25000)
-    ap.add_argument("--commit-every", type=int, default=10)
-    ap.add_argument("--cpu-sample", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the other BASELINE configs (N=1 only; ~2 min)")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive measurement (N=1 only)")
-    ap.add_argument("--inflight", type=int, default=2,
-                    help="contexts in flight per GPU (double buffering: one batch's decode stages run beside the other's integrate "
-                         "kernels); every step is still one full pipeline pass over one context's batch")
-    args = ap.parse_args()
-
+def dump_outputs(path, loop, out, k_last, seed=0, budget=48 << 20):
+    """--dump-outputs: what the last timed step handed to its caller, as float .npy files under `path` (every value is an integer
+    that the format holds exactly, so two builds can be compared value for value):
+      summary.npy        float64 [documents, 7] — the merged-state summary table the step returns, ordered by document id: id,
+                         status, pending ops, JSON length, version-vector length, and the device-side xxh64 of the JSON as two
+                         32-bit words (high, low)
+      sample_docs.npy    float64 [k] — rows of this rank's batch whose results are written out in full: a fixed, seeded choice
+      json_offsets.npy / vv_offsets.npy   float64 [k + 1] — where each sampled document's bytes begin in the arrays below
+      json_bytes.npy / vv_bytes.npy       float32 — the JSON and the encoded VersionVector of the sampled documents (lm_fetch of the
+                         context that ran the last step), one value per byte, concatenated
+    The sample stops growing before the files pass `budget` bytes."""
+    import ctypes
     import numpy as np
-    import torch
-    import torch.distributed as dist
-    import loro_amd
-    from loro_amd import dist as lmdist
+    os.makedirs(path, exist_ok=True)
+    table = StepLoop.host_table(out).astype(np.int64)
+    h = np.ascontiguousarray(table[:, 5]).view(np.uint64)
+    summary = np.empty((table.shape[0], 7), dtype=np.float64)
+    summary[:, :5] = table[:, :5]
+    summary[:, 5] = (h >> np.uint64(32)).astype(np.float64)
+    summary[:, 6] = (h & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    np.save(os.path.join(path, "summary.npy"), summary)
+    e = loop.engs[k_last]
+    e.fetch_raw()
+    order = np.random.default_rng(seed).permutation(e.n)[:64]
+    picked, js, vv, used = [], [], [], summary.nbytes
+    for i in order:
+        o = e._outs[int(i)]
+        used += 4 * (o.json_len + o.vv_len) + 24
+        if used > budget:
+            break
+        picked.append(int(i))
+        js.append(np.frombuffer(ctypes.string_at(o.json, o.json_len) if o.json_len else b"", dtype=np.uint8))
+        vv.append(np.frombuffer(ctypes.string_at(o.vv, o.vv_len) if o.vv_len else b"", dtype=np.uint8))
+    np.save(os.path.join(path, "sample_docs.npy"), np.asarray(picked, dtype=np.float64))
+    for name, parts in (("json", js), ("vv", vv)):
+        np.save(os.path.join(path, name + "_offsets.npy"), np.cumsum([0] + [len(x) for x in parts]).astype(np.float64))
+        np.save(os.path.join(path, name + "_bytes.npy"), np.concatenate(parts + [np.zeros(0, np.uint8)]).astype(np.float32))
+    note(f"outputs written to {path}: {table.shape[0]} summary rows, {len(picked)} documents in full")
 
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world > 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        dist.init_process_group(backend="nccl", rank=rank, world_size=world)
-    assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a HIP device: the merge engine has no CPU path")
-    torch.cuda.set_device(local_rank)
-    dev = torch.device("cuda", local_rank)
 
-    tpl, docs = build_docs(args.docs, rank * args.docs, args.base_ops, args.branch_ops, args.commit_every, seed=0)
-    doc_ids = list(range(rank * args.docs, (rank + 1) * args.docs))
-    note("documents built")
-    # CPU baseline first (rank 0 at N=1 only): its worker processes are forked before this process touches the GPU
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu, _ = cpu_baseline(docs, min(args.cpu_sample, len(docs)))
-    note("cpu baseline done" if cpu else "no cpu baseline")
-    engs = [loro_amd.MergeEngine(local_rank) for _ in range(max(1, args.inflight))]
-    for e in engs:
-        e.stage(docs)                     # blobs → HBM (outside the timed region); every context holds the batch
-        e.run()                           # first run of a context allocates its work pools (≈47 GB): part of set-up
+def full_report(args, line, loop, out, docs, cpu, dt, kavg, rank, world):
+    """--full, after the timed steps: the two serialized passes and the roofline of the dominant kernel, the parity check of the
+    timed batch against the oracle, the checks of the summary table and (N=1) the PCIe-inclusive leg.  Adds its entries to `line`."""
+    import numpy as np
+    engs = loop.engs
     eng = engs[0]
-    loop = StepLoop(engs, doc_ids, world, dev)
-    run_steps, timing = loop.run_steps, loop.timing
-
-    note("contexts staged")
-    run_steps(args.warmup)
-    for e in engs:
-        e.set_profiling(2)                 # stage events on the engine streams, streams overlapped as in production
-    timing["on"] = True
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = run_steps(args.steps)
-    torch.cuda.synchronize()
-    if world > 1:
-        dist.barrier()
-    dt = time.perf_counter() - t0
-    tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-    dt = float(tmax.item())
-
-    timing["on"] = False
-    note("timed steps done")
-    for e in engs:
-        e.set_profiling(0)
-    # ---- everything below is outside the timed region
-    st, jl, vl, pe = eng.result_meta()
-    assert int((st != 0).sum()) == 0, "documents failed on the device path"
+    n_streams = eng.b.n_streams(eng.h)
     stats = eng.stats()
     # per-kernel durations of the timed steps came from HIP events on the engine streams (timing["k"]); two extra passes
     # with the streams run one after the other give every stage's own duration for the breakdown
@@ -787,9 +762,7 @@ def main():
         for name, ms in eng.kernel_times():
             ktimes.setdefault(name, []).append(ms)
     eng.set_profiling(False)
-    n_streams = eng.b.n_streams(eng.h)
     kalone = {k: sum(v) / len(v) for k, v in ktimes.items()}           # one launch, nothing beside it
-    kavg = {k: sum(v) / len(v) for k, v in timing["k"].items()}        # one launch, averaged over the TIMED steps
     # The dominant kernel is the one with the largest SERIALIZED duration x launches per step (every stage is launched once per
     # stream, so the launch counts are equal and the serialized per-launch duration decides).  The overlapped HIP-event averages of
     # the timed steps are begin-to-end times of kernels sharing the GPU: a latency-bound stage that starts beside the integrate
@@ -829,7 +802,6 @@ def main():
         # (profiles/collect.sh sets it, so a stale record cannot be committed beside a line that names another kernel)
         note(f"WARNING: the dominant kernel here is {dom}, the newest committed PMC record ({prof_kernel[0]}) is of {prof_kernel[1]}: roofline.traffic is null")
         assert os.environ.get("LM_BENCH_STRICT", "0") in ("", "0"), f"dominant kernel {dom} != profiled kernel {prof_kernel[1]}"
-    line = None
     if rank == 0:
         # parity spot check of what was just timed (oracle = checker only)
         got = eng.fetch()
@@ -845,6 +817,136 @@ def main():
                 want = _oracle.merge_batch(docs[c0:min(n_chk, c0 + 2048)], threads=min(32, os.cpu_count() or 1))
                 assert got[c0:c0 + len(want)] == want, f"device results differ from the CPU oracle (documents {c0}..{c0 + len(want)})"
             parity_note = f"all {n_chk} documents of the timed batch equal to the oracle's (JSON, version vector, status, pending)"
+        line.update({
+            "roofline": {
+                "bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                "algorithmic_bytes_per_launch": int(alg_per_launch), "launches_per_step": n_streams,
+                "kernel_ms": round(k_ms, 3),
+                "kernel_ms_source": "HIP events on the engine stream, streams serialized (one launch, nothing beside it), after the timed steps",
+                "kernel_ms_rocprofv3": prof_alone,
+                "dominant_by": "largest serialized per-launch duration (kernels_ms_per_launch_alone); every stage is launched launches_per_step times per step",
+                "dominant_kernel_of_the_committed_profile": None if prof_kernel is None else {"file": prof_kernel[0], "kernel": prof_kernel[1], "same_kernel": prof_kernel[1] == dom},
+                "largest_overlapped_event_average": {"kernel": dom_overlapped, "ms": round(kavg.get(dom_overlapped, 0.0), 3),
+                                                     "note": "begin-to-end time while sharing the GPU with the other context's kernels; not used for frac"},
+                "kernel_ms_in_timed_region_overlapped": round(kavg.get(dom, k_ms), 3),
+                "frac_in_timed_region_overlapped": round(alg_per_launch / (kavg.get(dom, k_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                "pipeline_achieved": round(alg_bytes / (dt / args.steps) / 1e9, 2),
+                "pipeline_frac": round(alg_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
+            },
+            "parity": parity_note if world == 1 else "checked at N=1 (the oracle runs on rank 0's host cores)",
+            "kernels_ms_per_launch_alone": {k: round(v, 3) for k, v in kalone.items()},
+        })
+        if cpu is not None:
+            line["cpu_baseline"] = cpu
+            line["gpu_over_cpu"] = {"measured_on_available_cores": round(line["value"] / cpu["value"], 2),
+                                    "vs_linear_extrapolation_to_physical_cores": round(line["value"] / cpu["linear_extrapolation_to_physical_cores"]["value"], 2)}
+        n_total = args.docs * world
+        table = StepLoop.host_table(out)
+        assert table.shape[0] == n_total and (table[:, 1] == 0).all() and (table[:, 5] != 0).all()
+        if loop.dev_rows:
+            assert loop.device_rows_check(0), "summary rows written on the device differ from the host-side summary"
+            line["config"]["summary_exchange"] = "rows written by k_summary_rows into the send buffer; one all_gather_into_tensor of equal counts per step, result left on the device"
+        import xxhash
+        hashes = np.ascontiguousarray(table[:, 5]).view(np.uint64)
+        for i in (0, len(got) // 2, len(got) - 1):   # the summary's content word is the hash of what lm_fetch returns
+            assert int(hashes[i]) == xxhash.xxh64(got[i][1]).intdigest(), "device xxh64 differs from the fetched JSON's"
+        note("parity + summary checked")
+        if world == 1 and not args.no_end_to_end:
+            try:   # (a leg outside the metric: its failure is reported in its own entry and leaves the line alone)
+                line["end_to_end"] = end_to_end(engs, docs, max(16, args.steps))   # (fill and drain of the four-deep pipeline are inside the timed region: enough steps to see the steady state)
+            except Exception as ex:
+                line["end_to_end"] = {"error": f"{type(ex).__name__}: {ex}"[:300]}
+            note("end-to-end done")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--docs", type=int, default=10000, help="documents per GPU (configs[1]: 10,000)")
+    ap.add_argument("--base-ops", type=int, default=50000)
+    ap.add_argument("--branch-ops", type=int, default=25000)
+    ap.add_argument("--commit-every", type=int, default=10)
+    ap.add_argument("--cpu-sample", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: CPU baseline, parity of the timed batch against the oracle, the "
+                         "serialized passes of the roofline, the PCIe-inclusive measurement, the other configs (a few minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the other BASELINE configs (N=1 only; ~2 min)")
+    ap.add_argument("--no-end-to-end", action="store_true", help="with --full: skip the PCIe-inclusive measurement (N=1 only)")
+    ap.add_argument("--inflight", type=int, default=2,
+                    help="contexts in flight per GPU (double buffering: one batch's decode stages run beside the other's integrate "
+                         "kernels); every step is still one full pipeline pass over one context's batch")
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    import loro_amd
+    from loro_amd import dist as lmdist
+
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        dist.init_process_group(backend="nccl", rank=rank, world_size=world)
+    assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs a HIP device: the merge engine has no CPU path")
+    torch.cuda.set_device(local_rank)
+    dev = torch.device("cuda", local_rank)
+
+    tpl, docs = build_docs(args.docs, rank * args.docs, args.base_ops, args.branch_ops, args.commit_every, seed=0)
+    doc_ids = list(range(rank * args.docs, (rank + 1) * args.docs))
+    note("documents built")
+    # CPU baseline first (rank 0 at N=1 only): its worker processes are forked before this process touches the GPU
+    cpu = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        cpu, _ = cpu_baseline(docs, min(args.cpu_sample, len(docs)))
+    note("cpu baseline done" if cpu else "no cpu baseline")
+    engs = [loro_amd.MergeEngine(local_rank) for _ in range(max(1, args.inflight))]
+    for e in engs:
+        e.stage(docs)                     # blobs → HBM (outside the timed region); every context holds the batch
+        e.run()                           # first run of a context allocates its work pools (≈47 GB): part of set-up
+    eng = engs[0]
+    loop = StepLoop(engs, doc_ids, world, dev)
+    run_steps, timing = loop.run_steps, loop.timing
+
+    note("contexts staged")
+    run_steps(args.warmup)
+    for e in engs:
+        e.set_profiling(2)                 # stage events on the engine streams, streams overlapped as in production
+    timing["on"] = True
+    if world > 1:
+        dist.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = run_steps(args.steps)
+    torch.cuda.synchronize()
+    if world > 1:
+        dist.barrier()
+    dt = time.perf_counter() - t0
+    tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
+    if world > 1:
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+    dt = float(tmax.item())
+
+    timing["on"] = False
+    note("timed steps done")
+    for e in engs:
+        e.set_profiling(0)
+    # ---- everything below is outside the timed region
+    st, jl, vl, pe = eng.result_meta()
+    assert int((st != 0).sum()) == 0, "documents failed on the device path"
+    n_streams = eng.b.n_streams(eng.h)
+    kavg = {k: sum(v) / len(v) for k, v in timing["k"].items()}        # one launch, averaged over the TIMED steps (HIP events: no run of their own)
+    line = None
+    if rank == 0:
         n_total = args.docs * world
         line = {
             "metric": "merged docs/sec (batch of N docs x M remote ops)",
@@ -867,49 +969,15 @@ def main():
                 "sharding": f"doc-sharded x{world}, one all-gather of per-doc summaries per step" if world > 1 else "single GPU",
                 "contexts_in_flight": len(engs), "streams_per_context": n_streams,
             },
-            "roofline": {
-                "bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                "algorithmic_bytes_per_launch": int(alg_per_launch), "launches_per_step": n_streams,
-                "kernel_ms": round(k_ms, 3),
-                "kernel_ms_source": "HIP events on the engine stream, streams serialized (one launch, nothing beside it), after the timed steps",
-                "kernel_ms_rocprofv3": prof_alone,
-                "dominant_by": "largest serialized per-launch duration (kernels_ms_per_launch_alone); every stage is launched launches_per_step times per step",
-                "dominant_kernel_of_the_committed_profile": None if prof_kernel is None else {"file": prof_kernel[0], "kernel": prof_kernel[1], "same_kernel": prof_kernel[1] == dom},
-                "largest_overlapped_event_average": {"kernel": dom_overlapped, "ms": round(kavg.get(dom_overlapped, 0.0), 3),
-                                                     "note": "begin-to-end time while sharing the GPU with the other context's kernels; not used for frac"},
-                "kernel_ms_in_timed_region_overlapped": round(kavg.get(dom, k_ms), 3),
-                "frac_in_timed_region_overlapped": round(alg_per_launch / (kavg.get(dom, k_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "pipeline_achieved": round(alg_bytes / (dt / args.steps) / 1e9, 2),
-                "pipeline_frac": round(alg_bytes / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
-            },
-            "parity": parity_note if world == 1 else "checked at N=1 (the oracle runs on rank 0's host cores)",
             "kernels_ms_per_launch": {k: round(v, 3) for k, v in kavg.items()},
-            "kernels_ms_per_launch_alone": {k: round(v, 3) for k, v in kalone.items()},
         }
-        if cpu is not None:
-            line["cpu_baseline"] = cpu
-            line["gpu_over_cpu"] = {"measured_on_available_cores": round(line["value"] / cpu["value"], 2),
-                                    "vs_linear_extrapolation_to_physical_cores": round(line["value"] / cpu["linear_extrapolation_to_physical_cores"]["value"], 2)}
-        table = StepLoop.host_table(out)
-        assert table.shape[0] == n_total and (table[:, 1] == 0).all() and (table[:, 5] != 0).all()
-        if loop.dev_rows:
-            assert loop.device_rows_check(0), "summary rows written on the device differ from the host-side summary"
-            line["config"]["summary_exchange"] = "rows written by k_summary_rows into the send buffer; one all_gather_into_tensor of equal counts per step, result left on the device"
-        import xxhash
-        hashes = np.ascontiguousarray(table[:, 5]).view(np.uint64)
-        for i in (0, len(got) // 2, len(got) - 1):   # the summary's content word is the hash of what lm_fetch returns
-            assert int(hashes[i]) == xxhash.xxh64(got[i][1]).intdigest(), "device xxh64 differs from the fetched JSON's"
-        note("parity + summary checked")
-        if world == 1 and not args.no_end_to_end:
-            try:   # (a leg outside the metric: its failure is reported in its own entry and leaves the line alone)
-                line["end_to_end"] = end_to_end(engs, docs, max(16, args.steps))   # (fill and drain of the four-deep pipeline are inside the timed region: enough steps to see the steady state)
-            except Exception as ex:
-                line["end_to_end"] = {"error": f"{type(ex).__name__}: {ex}"[:300]}
-            note("end-to-end done")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, loop, out, (args.steps - 1) % len(engs) if args.steps > 0 else 0)
+    if args.full:
+        full_report(args, line, loop, out, docs, cpu, dt, kavg, rank, world)
     for e in engs:
         e.close()
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_other_configs:
         line["other_configs"] = other_configs(local_rank, host_cores()[0])
         note("other configs done")
         line["other_configs"].update(resident_configs(local_rank, host_cores()[0], n_docs=args.docs))

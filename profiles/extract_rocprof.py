@@ -5,9 +5,9 @@
 
 The three databases come from three separate runs of the SAME command, as the HBM section of
 /opt/skills/guides/MI355X_MICROARCH.md prescribes (FETCH_SIZE and WRITE_SIZE do not fit one pass):
-  rocprofv3 --kernel-trace --stats -d ... -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs --no-end-to-end
-  rocprofv3 --pmc FETCH_SIZE      -d ... -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --no-end-to-end
-  rocprofv3 --pmc WRITE_SIZE      -d ... -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-other-configs --no-end-to-end
+  rocprofv3 --kernel-trace --stats -d ... -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-other-configs --no-end-to-end
+  rocprofv3 --pmc FETCH_SIZE      -d ... -- python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs --no-end-to-end
+  rocprofv3 --pmc WRITE_SIZE      -d ... -- python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-other-configs --no-end-to-end
 FETCH_SIZE / WRITE_SIZE are in KiB.  gfx950 correction from the guide: FETCH_SIZE under-reports wide coalesced
 reads by 2x; the corrected figure doubles it (other access widths are uncalibrated — both figures are kept).
 """
@@ -23,7 +23,7 @@ def main():
     for name, calls, tot, avg, pct in rows:
         out["kernels"][name] = {"calls": calls, "avg_ms": round(avg / 1e3, 4), "total_ms": round(tot / 1e3, 3), "pct": round(pct, 2)}
         lines.append(f"| {name} | {calls} | {tot / 1e3:.3f} | {avg / 1e3:.4f} | {pct:.2f} |")
-    # bench.py ends with two passes in which the context's streams run one after the other (lm_set_profiling(1)): the last
+    # bench.py --full ends with two passes in which the context's streams run one after the other (lm_set_profiling(1)): the last
     # 2 x n_streams dispatches of a pipeline kernel are launches with nothing beside them — the figure bench.py's roofline uses
     # (kernel_ms / kernel_ms_alone); the average over ALL dispatches mixes set-up, overlapped timed steps and those passes
     alone_lines = ["", "## the serialized passes at the end of the command (last 4 dispatches per kernel: 2 passes x 2 streams, nothing beside them)", "",

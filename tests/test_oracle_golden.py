@@ -146,10 +146,9 @@ def test_errors_mirror_loro_error_kinds():
     assert _oracle.merge([good[:10]])[0] == 1                # DecodeError: too short
 
 
-REF_TRACE = "/root/reference/crates/loro-internal/benches/automerge-paper.json.gz"
+REF_TRACE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "automerge-paper.json.gz")   # the reference's crates/loro-internal/benches/automerge-paper.json.gz, stored as it is
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TRACE), reason="reference benchmark trace only exists in the build container")
 def test_automerge_paper_trace_end_content():
     """benches/automerge-paper.json.gz: applying all 259,778 patches must give `endContent`."""
     d = json.load(gzip.open(REF_TRACE))
