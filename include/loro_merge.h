@@ -262,6 +262,94 @@ void lm_free_bytes(uint8_t* p);
 int lm_richtext(lm_ctx* ctx);
 int lm_richtext_result(lm_ctx* ctx, size_t doc, int32_t* status, const uint8_t** json, size_t* json_len);
 
+/* ---- Stable cursors: carets, selections, comment anchors re-anchored after a merge without a second replay on the host.  A Loro
+ * `Cursor` is an element id plus a side (crates/loro-internal/src/cursor.rs); LoroDoc::get_cursor_pos resolves it
+ * (crates/loro-internal/src/loro.rs:1860-1994 -> state.rs:2061-2091), TextHandler / ListHandler::get_cursor mints it
+ * (handler.rs:2673-2735, 3393-3433).  Both calls are valid after lm_run and answer AT THE VERSION THAT RUN RENDERED (the latest
+ * version or the entry's checkout; for resident documents the state after the last lm_import + lm_run), on the device, from the
+ * trackers the run left (k_cursor: one wave per document that has queries, one pass over a container's leaves per 64 queries,
+ * loro_amd/csrc/lm_k_cursor.h).  A query names its document (index into the batch staged last) and its container by the
+ * ContainerID Display bytes lm_richtext_result uses as keys, unescaped: cid:root-<name>:Text, cid:<counter>@<peer>:List.
+ *
+ * lm_cursor_pos, per query (status, pos, pos_utf16, side):
+ *   - the id is visible at that version: LM_CURSOR_OK, pos = its index among the container's visible elements — the Unicode scalar
+ *     index for a Text (style anchors occupy ids but never count: the entity index -> event index conversion, handler.rs:2737-2745),
+ *     the element index for a List; pos_utf16 = the same position in UTF-16 code units (one more per visible scalar >= U+10000 in
+ *     front of it; == pos for a List); side is echoed (loro.rs:1875-1882);
+ *   - the id is in the tracker but not visible (deleted at that version): LM_CURSOR_DELETED, pos = the number of visible elements in
+ *     front of the tombstone in sequence order, side = Left (tracker.rs:608-639 get_target_id_latest_index; loro.rs:1936-1959).  The
+ *     `update` cursor the reference adds is lm_cursor_at of that pos and side;
+ *   - the version does not contain the id: LM_CURSOR_ID_NOT_FOUND (loro.rs:1911-1917) — a counter at or beyond that version's
+ *     end for its peer, an id the checkout leaves in the future, an unknown peer, an id inside the known range that belongs to
+ *     another container or to an op that creates no element (a delete, a Map write);
+ *   - has_id == 0: LM_CURSOR_OK, pos = 0 for side Left, otherwise the container's length (state.rs:2073-2090).
+ * An id that names a style anchor resolves to the number of visible scalars in front of the anchor (OK / DELETED like any element);
+ * nothing the reference holds pins this case.
+ *
+ * lm_cursor_at(pos, side) — pos a Unicode scalar / element index — follows handler.rs:2704-2733:
+ *   - empty container: no id, side Middle becomes Left, origin_pos 0;
+ *   - pos >= len: no id, side Right, origin_pos = len;
+ *   - otherwise the id of the visible element at pos, side echoed, origin_pos = pos.
+ *
+ * Other statuses, never a guessed position: LM_CURSOR_CONTAINER_NOT_FOUND (no such container in the document, or a key that is no
+ * ContainerID), LM_CURSOR_DOC_FAILED (the document's import or checkout failed; an LM_UNSUPPORTED document that was rendered still
+ * answers for its Text / List containers), LM_CURSOR_UNSUPPORTED (see Limits).  Both calls return 0, or -1 (lm_last_error) for a
+ * call that cannot be answered at all: before lm_run, a document index beyond the batch, a side outside -1..1.
+ *
+ * Batch shapes are lm_richtext's: a batch folded by shared replay is unfolded first; documents staged from a snapshot's STATE
+ * section (no element ids) are staged once more through their history and run again; documents replayed in the side engine
+ * (lm_redo_documents) are answered there.  One more: the batch kernels replay a long single-writer prefix of a history as a
+ * positional rope that DROPS what it deletes (the reference's unknown span has no tombstones either, tracker.rs:40-62); the first
+ * cursor call on a batch that holds such a document (2,048 op rows or more) runs the batch once more with that prefix switched off
+ * and the context keeps it off until the next lm_stage (a host that knows it will ask sets LM_LINEAR=0 in the environment and
+ * never pays the second run; resident documents, lm_import, never go through that prefix).  In all three cases lm_fetch / lm_result_meta give the same bytes as before
+ * and the calls change nothing lm_run wrote: the kernel reads tracker memory and writes only its own result rows.
+ * Limits: Map, Tree and Counter containers have no element ids, a MovableList names its elements through a second id space
+ * (movable_list_state.rs:941) — both LM_CURSOR_UNSUPPORTED, like every container of a document that is LM_UNSUPPORTED without a
+ * rendering (a shallow snapshot, an engine limit); a Text / List container that never received an op is not in the document's
+ * container table: LM_CURSOR_CONTAINER_NOT_FOUND. */
+enum {
+  LM_CURSOR_OK = 0,
+  LM_CURSOR_DELETED = 1,
+  LM_CURSOR_ID_NOT_FOUND = 2,        /* CannotFindRelativePosition::IdNotFound */
+  LM_CURSOR_CONTAINER_NOT_FOUND = 3, /* CannotFindRelativePosition::ContainerDeleted / no such container */
+  LM_CURSOR_DOC_FAILED = 4,
+  LM_CURSOR_UNSUPPORTED = 5
+};
+typedef struct lm_cursor_query {
+  size_t doc;               /* index into the batch staged last */
+  const uint8_t* container; /* ContainerID Display bytes (not NUL terminated) */
+  size_t container_len;
+  int32_t has_id;           /* 0: Cursor.id == None (a cursor taken on an empty container or behind the end) */
+  uint64_t peer;            /* Cursor.id */
+  int32_t counter;
+  int32_t side;             /* -1 Left, 0 Middle, 1 Right (cursor.rs Side) */
+} lm_cursor_query;
+typedef struct lm_cursor_result {
+  int32_t status;           /* LM_CURSOR_* */
+  uint32_t pos;             /* PosQueryResult.current.pos */
+  uint32_t pos_utf16;
+  int32_t side;             /* PosQueryResult.current.side */
+} lm_cursor_result;
+typedef struct lm_cursor_at_query {
+  size_t doc;
+  const uint8_t* container;
+  size_t container_len;
+  uint32_t pos;             /* Unicode scalar index (Text) / element index (List) */
+  int32_t side;
+} lm_cursor_at_query;
+typedef struct lm_cursor_at_result {
+  int32_t status;           /* LM_CURSOR_OK, _CONTAINER_NOT_FOUND, _DOC_FAILED, _UNSUPPORTED */
+  int32_t has_id;
+  uint64_t peer;            /* Cursor.id when has_id */
+  int32_t counter;
+  int32_t side;             /* Cursor.side */
+  uint32_t origin_pos;      /* Cursor.origin_pos */
+  uint32_t reserved;
+} lm_cursor_at_result;
+int lm_cursor_pos(lm_ctx* ctx, const lm_cursor_query* queries, size_t n, lm_cursor_result* out);
+int lm_cursor_at(lm_ctx* ctx, const lm_cursor_at_query* queries, size_t n, lm_cursor_at_result* out);
+
 /* Wave-primitive self test on the device (DPP scan, ballot ranks); returns the number of mismatches. */
 int lm_selftest(lm_ctx* ctx);
 

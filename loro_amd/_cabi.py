@@ -19,9 +19,30 @@ class RunStats(ctypes.Structure):
                 ("device_bytes_allocated", ctypes.c_uint64), ("n_kernels", ctypes.c_uint32)]
 
 
+class CursorQuery(ctypes.Structure):
+    _fields_ = [("doc", ctypes.c_size_t), ("container", ctypes.c_char_p), ("container_len", ctypes.c_size_t), ("has_id", ctypes.c_int32),
+                ("peer", ctypes.c_uint64), ("counter", ctypes.c_int32), ("side", ctypes.c_int32)]
+
+
+class CursorResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("pos", ctypes.c_uint32), ("pos_utf16", ctypes.c_uint32), ("side", ctypes.c_int32)]
+
+
+class CursorAtQuery(ctypes.Structure):
+    _fields_ = [("doc", ctypes.c_size_t), ("container", ctypes.c_char_p), ("container_len", ctypes.c_size_t), ("pos", ctypes.c_uint32), ("side", ctypes.c_int32)]
+
+
+class CursorAtResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("has_id", ctypes.c_int32), ("peer", ctypes.c_uint64), ("counter", ctypes.c_int32), ("side", ctypes.c_int32),
+                ("origin_pos", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+CURSOR_OK, CURSOR_DELETED, CURSOR_ID_NOT_FOUND, CURSOR_CONTAINER_NOT_FOUND, CURSOR_DOC_FAILED, CURSOR_UNSUPPORTED = range(6)
+
 SYMBOLS = ["create", "destroy", "last_error", "merge_batch", "stage", "run", "fetch", "get_stats", "set_profiling", "kernel_time", "selftest", "result_meta", "result_hashes", "n_streams", "run_async", "wait",
            "encode_block", "encode_updates", "free_bytes", "import", "resident_fresh", "import_modes", "import_lca", "export", "comm_unique_id", "comm_init", "summary_allgather",
-           "summary_layout", "summary_rows_device", "summary_allgather_device", "shared_documents", "richtext", "richtext_result", "fused_documents", "redo_documents", "state_documents", "host_alloc", "host_free", "staged_direct"]
+           "summary_layout", "summary_rows_device", "summary_allgather_device", "shared_documents", "richtext", "richtext_result", "fused_documents", "redo_documents", "state_documents", "host_alloc", "host_free", "staged_direct",
+           "cursor_pos", "cursor_at"]
 
 
 class Binding:
@@ -58,6 +79,10 @@ class Binding:
         self.richtext = g("richtext"); self.richtext.restype = ctypes.c_int; self.richtext.argtypes = [ctypes.c_void_p]
         self.richtext_result = g("richtext_result"); self.richtext_result.restype = ctypes.c_int
         self.richtext_result.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        self.cursor_pos = g("cursor_pos"); self.cursor_pos.restype = ctypes.c_int
+        self.cursor_pos.argtypes = [ctypes.c_void_p, ctypes.POINTER(CursorQuery), ctypes.c_size_t, ctypes.POINTER(CursorResult)]
+        self.cursor_at = g("cursor_at"); self.cursor_at.restype = ctypes.c_int
+        self.cursor_at.argtypes = [ctypes.c_void_p, ctypes.POINTER(CursorAtQuery), ctypes.c_size_t, ctypes.POINTER(CursorAtResult)]
         self.comm_unique_id = g("comm_unique_id"); self.comm_unique_id.restype = ctypes.c_int; self.comm_unique_id.argtypes = [ctypes.c_char_p]
         self.comm_init = g("comm_init"); self.comm_init.restype = ctypes.c_int; self.comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
         self.summary_allgather = g("summary_allgather"); self.summary_allgather.restype = ctypes.c_long
@@ -241,6 +266,36 @@ class Context:
                 raise RuntimeError(self.b.last_error(self.h).decode())
             out.append((st.value, ctypes.string_at(p.value, n.value) if n.value else b""))
         return out
+
+    def cursor_pos(self, queries):
+        """lm_cursor_pos (LoroDoc::get_cursor_pos) at the version the last run rendered.  queries: [(doc, container id, id, side)] —
+        container id = ContainerID Display ("cid:root-text:Text"; str or bytes), id = (peer, counter) or None, side -1 / 0 / 1.
+        Returns [(status, pos, pos_utf16, side)], status = CURSOR_*."""
+        n = len(queries)
+        qs, out, keep = (CursorQuery * max(n, 1))(), (CursorResult * max(n, 1))(), []
+        for k, (doc, cid, id_, side) in enumerate(queries):
+            cid = cid.encode() if isinstance(cid, str) else bytes(cid)
+            keep.append(cid)
+            qs[k].doc = doc; qs[k].container = cid; qs[k].container_len = len(cid); qs[k].side = side
+            qs[k].has_id = 0 if id_ is None else 1
+            if id_ is not None:
+                qs[k].peer, qs[k].counter = id_
+        if self.b.cursor_pos(self.h, qs, n, out) != 0:
+            raise RuntimeError(self.b.last_error(self.h).decode())
+        return [(out[k].status, out[k].pos, out[k].pos_utf16, out[k].side) for k in range(n)]
+
+    def cursor_at(self, queries):
+        """lm_cursor_at (TextHandler / ListHandler::get_cursor) at the version the last run rendered.  queries: [(doc, container id,
+        pos, side)].  Returns [(status, id, side, origin_pos)], id = (peer, counter) or None."""
+        n = len(queries)
+        qs, out, keep = (CursorAtQuery * max(n, 1))(), (CursorAtResult * max(n, 1))(), []
+        for k, (doc, cid, pos, side) in enumerate(queries):
+            cid = cid.encode() if isinstance(cid, str) else bytes(cid)
+            keep.append(cid)
+            qs[k].doc = doc; qs[k].container = cid; qs[k].container_len = len(cid); qs[k].pos = pos; qs[k].side = side
+        if self.b.cursor_at(self.h, qs, n, out) != 0:
+            raise RuntimeError(self.b.last_error(self.h).decode())
+        return [(out[k].status, (out[k].peer, out[k].counter) if out[k].has_id else None, out[k].side, out[k].origin_pos) for k in range(n)]
 
     def comm_init(self, rank=0, world=1, unique_id=None):
         if self.b.comm_init(self.h, rank, world, unique_id or bytes(128)) != 0:

@@ -136,6 +136,8 @@ struct lm_ctx_impl {
     lm::Engine& a = *rd.eng;
     a.force_span = true;
     a.profiling = profiling != 0;
+    a.keep_tombstones = false;
+    for (uint32_t p = 0; p < n_parts(); p++) a.keep_tombstones |= parts[p]->keep_tombstones;   // (lm_cursor_pos asked for a replay that keeps what it deletes)
     a.stage_from(parents, items);
     a.run();
     rd.res = a.results;
@@ -292,7 +294,7 @@ struct lm_ctx_impl {
     mapped = false;
     rd.on = false;
     sum_rows_padded = 0;             // (a new batch: lm_summary_layout is called again for it)
-    for (auto& pt : parts) pt->sum_rows = nullptr;
+    for (auto& pt : parts) { pt->sum_rows = nullptr; pt->keep_tombstones = false; }
     // split into contiguous ranges of about equal blob bytes; small batches stay in one part
     uint64_t total = 0;
     for (size_t i = 0; i < n; i++) for (size_t b = 0; b < docs[i].n; b++) total += docs[i].lens[b];
@@ -472,6 +474,91 @@ struct lm_ctx_impl {
     if (mapped) { for (uint32_t i = 0; i < n_docs; i++) f(i, *parts[emap[i].first], parts[emap[i].first]->results[emap[i].second]); return; }
     for (uint32_t p = 0; p < n_parts(); p++)
       for (uint32_t i = 0; i < parts[p]->n_docs; i++) f(first[p] + i, *parts[p], parts[p]->results[i]);
+  }
+
+  // ---- lm_cursor_pos / lm_cursor_at (lm_k_cursor.h).  The batch shapes are lm_richtext's: documents staged from a snapshot's STATE
+  // hold no element ids (staged once more through their history), a folded batch is unfolded (the trackers have to stand at every
+  // entry's version), documents replayed in the side engine are answered there.  One more: a batch whose documents may have gone
+  // through the linear prefix is run again without it (Engine::cursor_needs_tombstones).  The results of lm_fetch / lm_result_meta
+  // are that run's from here on — the same bytes.
+  void cursor_prepare() {
+    if (!ran) throw std::runtime_error("lm_cursor_pos / lm_cursor_at before lm_run");
+    if (in_flight) throw std::runtime_error("lm_cursor_pos / lm_cursor_at while a run is in flight");
+    bool any = false;
+    for (uint32_t p = 0; p < n_parts(); p++) if (parts[p]->n_state_docs && !parts[p]->resident) { parts[p]->restage_history(); any = true; }
+    if (!sh.on) for (uint32_t p = 0; p < n_parts(); p++) if (parts[p]->cursor_needs_tombstones()) { parts[p]->keep_tombstones = true; any = true; }
+    if (any) { run(); sum_host_rows(); }
+    if (sh.on) { unfold(); ran = true; sum_host_rows(); }
+    if (rd.on && rd.eng->cursor_needs_tombstones()) { rd.eng->keep_tombstones = true; rd.eng->run(); }
+  }
+  // ContainerID Display (loro-common/src/lib.rs: cid:root-<name>:<Type> / cid:<counter>@<peer>:<Type>) -> the query's container fields
+  static void cursor_key(const uint8_t* k, size_t n, lm::Engine::CursorKey& q) {
+    q.ok = false;
+    if (!k || n < 5 || memcmp(k, "cid:", 4) != 0) return;
+    size_t colon = n;
+    while (colon > 4 && k[colon - 1] != ':') colon--;
+    if (colon <= 4) return;
+    const std::string ty((const char*)k + colon, n - colon);
+    uint32_t kind;
+    if (ty == "Map") kind = lm::CK_MAP; else if (ty == "List") kind = lm::CK_LIST; else if (ty == "Text") kind = lm::CK_TEXT; else if (ty == "Tree") kind = lm::CK_TREE;
+    else if (ty == "MovableList") kind = lm::CK_MOVABLE; else if (ty == "Counter") kind = lm::CK_COUNTER; else return;
+    const size_t body_end = colon - 1;   // [4, body_end) = root-<name> | <counter>@<peer>
+    if (body_end >= 9 && memcmp(k + 4, "root-", 5) == 0) {
+      q.kind_root = kind | 0x100; q.name.assign((const char*)k + 9, body_end - 9); q.ok = true;
+      return;
+    }
+    size_t at = 4;
+    bool neg = false;
+    if (at < body_end && k[at] == '-') { neg = true; at++; }
+    uint64_t ctr = 0, peer = 0;
+    size_t d0 = at;
+    while (at < body_end && k[at] >= '0' && k[at] <= '9' && ctr < (1ull << 32)) ctr = ctr * 10 + (k[at++] - '0');
+    if (at == d0 || at >= body_end || k[at] != '@' || ctr > (1ull << 31)) return;
+    at++;
+    d0 = at;
+    while (at < body_end && k[at] >= '0' && k[at] <= '9') { if (peer > (~0ull - 9) / 10) return; peer = peer * 10 + (k[at++] - '0'); }
+    if (at == d0 || at != body_end) return;
+    q.kind_root = kind; q.cpeer = peer; q.ccounter = (uint32_t)(neg ? -(int64_t)ctr : (int64_t)ctr); q.ok = true;
+  }
+  // the container keys of one call, interned: queries name their container by an index (a caller usually repeats one pointer many times)
+  struct CursorKeys {
+    std::vector<lm::Engine::CursorKey> keys;
+    std::map<std::string, uint32_t> ids;
+    const uint8_t* last_p = nullptr; size_t last_n = 0; uint32_t last_id = 0;
+    uint32_t intern(const uint8_t* p, size_t n) {
+      if (p == last_p && n == last_n && !keys.empty()) return last_id;
+      auto it = ids.emplace(p ? std::string((const char*)p, n) : std::string(), (uint32_t)keys.size());
+      if (it.second) { keys.emplace_back(); cursor_key(p, n, keys.back()); }
+      last_p = p; last_n = n; last_id = it.first->second;
+      return last_id;
+    }
+  };
+  // in[k].doc = API document; out[k] answers in[k]
+  void cursor(const std::vector<lm::Engine::CursorKey>& keys, std::vector<lm::Engine::CursorIn>& in, std::vector<lm::CurRes>& out, bool at) {
+    cursor_prepare();
+    out.assign(in.size(), lm::CurRes{lm::CUR_DOC_FAILED, 0, 0, 0, 0, 0, 0, 0, 0});
+    std::vector<std::vector<uint32_t>> of(n_parts() + 1);   // the queries of every part; the last list is the side engine's
+    for (size_t k = 0; k < in.size(); k++) {
+      const size_t doc = in[k].doc;
+      if (doc >= api_docs()) throw std::runtime_error("lm_cursor_pos / lm_cursor_at: no such document");
+      if (redone(doc)) { in[k].doc = (uint32_t)rd.of[doc]; of[n_parts()].push_back((uint32_t)k); continue; }
+      uint32_t p = 0;
+      if (mapped) { p = emap[doc].first; in[k].doc = emap[doc].second; }
+      else { while (p + 1 < n_parts() && doc >= first[p + 1]) p++; in[k].doc = (uint32_t)(doc - first[p]); }
+      of[p].push_back((uint32_t)k);
+    }
+    std::vector<lm::Engine::CursorIn> sub;
+    std::vector<lm::CurRes> r;
+    for (uint32_t p = 0; p <= n_parts(); p++) {
+      if (of[p].empty()) continue;
+      lm::Engine& e = p < n_parts() ? *parts[p] : *rd.eng;
+      e.profiling = profiling != 0;
+      sub.clear();
+      for (uint32_t k : of[p]) sub.push_back(in[k]);
+      e.cursor(keys, sub, r, at);
+      for (size_t j = 0; j < of[p].size(); j++) out[of[p][j]] = r[j];
+      if (profiling) times.push_back(lm::KernelTime{"k_cursor", e.cur_ms});
+    }
   }
 };
 
@@ -773,6 +860,63 @@ int LM_API(richtext_result)(void* c, size_t doc, int32_t* status, const uint8_t*
       return 0;
     }
     throw std::runtime_error("lm_richtext_result: no such document");
+  } catch (const std::exception& e) { x->err = e.what(); return -1; }
+}
+// ---- Stable cursors (include/loro_merge.h): resolved on the device from the trackers of the last lm_run (lm_k_cursor.h)
+typedef struct lm_cursor_query_c { size_t doc; const uint8_t* container; size_t container_len; int32_t has_id; uint64_t peer; int32_t counter; int32_t side; } lm_cursor_query_c;
+typedef struct lm_cursor_result_c { int32_t status; uint32_t pos, pos_utf16; int32_t side; } lm_cursor_result_c;
+typedef struct lm_cursor_at_query_c { size_t doc; const uint8_t* container; size_t container_len; uint32_t pos; int32_t side; } lm_cursor_at_query_c;
+typedef struct lm_cursor_at_result_c { int32_t status; int32_t has_id; uint64_t peer; int32_t counter; int32_t side; uint32_t origin_pos; uint32_t pad; } lm_cursor_at_result_c;
+int LM_API(cursor_pos)(void* c, const lm_cursor_query_c* qs, size_t n, lm_cursor_result_c* out) {
+  auto* x = (lm_ctx_impl*)c;
+  try {
+    std::vector<lm::Engine::CursorIn> in(n);
+    lm_ctx_impl::CursorKeys ck;
+    for (size_t k = 0; k < n; k++) {
+      if (qs[k].side < -1 || qs[k].side > 1) throw std::runtime_error("lm_cursor_pos: side is -1 (Left), 0 (Middle) or 1 (Right)");
+      if (qs[k].doc >= x->api_docs()) throw std::runtime_error("lm_cursor_pos: no such document");
+      in[k].doc = (uint32_t)qs[k].doc;
+      in[k].key = ck.intern(qs[k].container, qs[k].container_len);
+      in[k].has_id = qs[k].has_id ? 1u : 0u; in[k].peer = qs[k].peer;
+      in[k].ctr = qs[k].counter < 0 ? lm::NONE : (uint32_t)qs[k].counter;   // (no element has a negative counter: LM_CURSOR_ID_NOT_FOUND)
+    }
+    std::vector<lm::CurRes> r;
+    x->cursor(ck.keys, in, r, false);
+    for (size_t k = 0; k < n; k++) {
+      lm_cursor_result_c& o = out[k];
+      o.status = r[k].status; o.pos = 0; o.pos_utf16 = 0; o.side = qs[k].side;
+      if (r[k].status == lm::CUR_OK && !qs[k].has_id) { if (qs[k].side != -1) { o.pos = r[k].len; o.pos_utf16 = r[k].len16; } }   // state.rs:2073-2090
+      else if (r[k].status == lm::CUR_OK) { o.pos = r[k].pos; o.pos_utf16 = r[k].pos16; }
+      else if (r[k].status == lm::CUR_DELETED) { o.pos = r[k].pos; o.pos_utf16 = r[k].pos16; o.side = -1; }   // tracker.rs:608-639: Side::Left
+    }
+    return 0;
+  } catch (const std::exception& e) { x->err = e.what(); return -1; }
+}
+int LM_API(cursor_at)(void* c, const lm_cursor_at_query_c* qs, size_t n, lm_cursor_at_result_c* out) {
+  auto* x = (lm_ctx_impl*)c;
+  try {
+    std::vector<lm::Engine::CursorIn> in(n);
+    lm_ctx_impl::CursorKeys ck;
+    for (size_t k = 0; k < n; k++) {
+      if (qs[k].side < -1 || qs[k].side > 1) throw std::runtime_error("lm_cursor_at: side is -1 (Left), 0 (Middle) or 1 (Right)");
+      if (qs[k].doc >= x->api_docs()) throw std::runtime_error("lm_cursor_at: no such document");
+      in[k].doc = (uint32_t)qs[k].doc;
+      in[k].key = ck.intern(qs[k].container, qs[k].container_len);
+      in[k].peer = 0; in[k].has_id = 0;
+      in[k].ctr = qs[k].pos;
+    }
+    std::vector<lm::CurRes> r;
+    x->cursor(ck.keys, in, r, true);
+    for (size_t k = 0; k < n; k++) {
+      lm_cursor_at_result_c& o = out[k];
+      o.status = r[k].status; o.has_id = 0; o.peer = 0; o.counter = 0; o.side = qs[k].side; o.origin_pos = 0; o.pad = 0;
+      if (r[k].status != lm::CUR_OK) continue;
+      // handler.rs:2704-2733
+      if (r[k].len == 0) { o.side = qs[k].side == 0 ? -1 : qs[k].side; }
+      else if (!r[k].has) { o.side = 1; o.origin_pos = r[k].len; }
+      else { o.has_id = 1; o.peer = r[k].peer; o.counter = (int32_t)r[k].ctr; o.origin_pos = qs[k].pos; }
+    }
+    return 0;
   } catch (const std::exception& e) { x->err = e.what(); return -1; }
 }
 int LM_API(get_stats)(void* c, lm_run_stats_c* s) {

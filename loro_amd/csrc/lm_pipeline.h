@@ -24,6 +24,7 @@
 #include "lm_k_fuse.h"
 #include "lm_k_lca.h"
 #include "lm_k_richtext.h"
+#include "lm_k_cursor.h"
 #include "lm_snapshot.h"
 #include "lm_export.h"
 #include "lm_snapshot_base.h"
@@ -126,6 +127,10 @@ struct Engine {
   std::vector<int32_t> h_rt_status;
   bool rt_ran = false;
   int rt_launches = 0;                            // k_richtext launches of the last lm_richtext (2: a slab was too small)
+  // lm_cursor_pos / lm_cursor_at (lm_k_cursor.h)
+  DBuf b_cur_doc, b_cur_dg, b_cur_grp, b_cur_q, b_cur_names, b_cur_res;
+  bool keep_tombstones = false;                   // the next runs replay without the linear prefix (it drops what it deletes from the leaves: cursor_needs_tombstones)
+  double cur_ms = 0;                              // k_cursor of the last call (profiling)
   std::vector<KernelTime> times;
   bool profiling = false;
   std::string last_error;
@@ -1160,7 +1165,7 @@ struct Engine {
     // slice, as resident documents always do — they keep loc[] between runs).  cp[] needs no fill: every element that can be
     // placed was written by k_elem_fill
     d.loc_cleared = (!resident && span && kn.loc_memset) ? 1u : 0u;
-    d.no_linear = kn.linear ? 0u : 1u;
+    d.no_linear = kn.linear && !keep_tombstones ? 0u : 1u;
     d.posdel_redo = (kn.redo && kn.posdel && st_valid && (resident ? shared_mode != 0 : !span)) ? 1u : 0u;
     d.posdel_off = nullptr; d.pd_row_idx = nullptr;
     if (span && !resident && kn.posdel) {
@@ -1685,6 +1690,98 @@ struct Engine {
       tmp.push_back('}');
       if (tmp.size() == n) memcpy(p, tmp.data(), n); else h_rt_status[i] = ST_INTERNAL;
     }
+  }
+
+  // ---- lm_cursor_pos / lm_cursor_at (lm_k_cursor.h): ids -> positions, positions -> ids, from the trackers the last run left.
+  // The linear prefix of the plain batch kernels (lm_k_integrate_linear.h) REMOVES what it deletes from the leaves, as the reference's
+  // unknown span has no tombstones either; a cursor on a deleted element needs the tombstone.  A batch in which a document may have
+  // gone through the prefix (DF_CUT) is therefore run once more without it (the context does that: same bytes out), and stays
+  // without it until the next lm_stage.  Resident documents never go through the prefix.
+  bool cursor_needs_tombstones() const {
+    if (resident || keep_tombstones || !kn.linear || !ran || !last_d.span) return false;
+    for (uint32_t i = 0; i < n_docs && i < h_doc.size(); i++) if (h_doc[i].status == ST_OK && (h_doc[i].flags & DF_CUT)) return true;
+    return false;
+  }
+  struct CursorKey {            // a query's container: the parsed ContainerID (the context interns the keys of a call)
+    bool ok = false;             // the key parsed as a ContainerID
+    uint32_t kind_root = 0;      // kind | is_root << 8
+    std::string name;            // root container
+    uint64_t cpeer = 0;          // normal container
+    uint32_t ccounter = 0;
+  };
+  struct CursorIn {
+    uint32_t doc;                // document of this engine
+    uint32_t key;                // index into the call's keys
+    uint64_t peer;               // the cursor's id (lm_cursor_at: ctr = the position)
+    uint32_t ctr, has_id;
+  };
+  // out[k] answers in[k]; queries the host can answer (a failed document, a key that names no sequence container) never reach the device
+  void cursor(const std::vector<CursorKey>& keys, const std::vector<CursorIn>& in, std::vector<CurRes>& out, bool at) {
+    lmbe::bind(sc);
+    if (!ran) throw std::runtime_error("lm_cursor_pos / lm_cursor_at before lm_run");
+    if (shared_mode != 0) throw std::runtime_error("lm_cursor_pos: a folded batch has to be unfolded first");
+    out.assign(in.size(), CurRes{CUR_DOC_FAILED, 0, 0, 0, 0, 0, 0, 0, 0});
+    cur_ms = 0;
+    std::vector<uint32_t> idx;
+    idx.reserve(in.size());
+    for (size_t k = 0; k < in.size(); k++) {
+      const CursorIn& q = in[k];
+      if (q.doc >= n_docs || q.key >= keys.size()) throw std::runtime_error("lm_cursor_pos / lm_cursor_at: no such document");
+      const DocMeta& m = h_doc[q.doc];
+      const CursorKey& ck = keys[q.key];
+      const uint32_t kind = ck.kind_root & 0xff;
+      if (m.status != ST_OK || (m.flags & DF_FRONT_ERR)) out[k].status = m.status == ST_UNSUPPORTED ? CUR_UNSUPPORTED : CUR_DOC_FAILED;
+      else if (!ck.ok) out[k].status = CUR_CONTAINER_NOT_FOUND;
+      else if (kind != CK_TEXT && kind != CK_LIST) out[k].status = CUR_UNSUPPORTED;
+      else if (q.doc < h_fused.size() && h_fused[q.doc]) out[k].status = CUR_CONTAINER_NOT_FOUND;   // (an LWW Map document decoded without op rows: Maps only)
+      else idx.push_back((uint32_t)k);
+    }
+    if (idx.empty()) return;
+    // by (document, container); a caller that lists its queries document by document is in order already
+    auto ord = [&](uint32_t k) { return ((uint64_t)in[k].doc << 32) | in[k].key; };
+    if (!std::is_sorted(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return ord(a) < ord(b); }))
+      std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return ord(a) < ord(b); });
+    std::vector<uint32_t> qdoc, dg0;
+    std::vector<CurGroup> grp;
+    std::vector<CurQuery> qs(idx.size());
+    std::vector<uint8_t> names;
+    for (size_t k = 0; k < idx.size(); k++) {
+      const CursorIn& q = in[idx[k]];
+      const bool new_doc = k == 0 || in[idx[k - 1]].doc != q.doc;
+      if (new_doc) { qdoc.push_back(q.doc); dg0.push_back((uint32_t)grp.size()); }
+      if (new_doc || in[idx[k - 1]].key != q.key) {
+        const CursorKey& ck = keys[q.key];
+        CurGroup g;
+        g.q0 = (uint32_t)k; g.nq = 0; g.kind_root = ck.kind_root; g.counter = ck.ccounter; g.peer = ck.cpeer;
+        g.name_off = (uint32_t)names.size(); g.name_len = (uint32_t)ck.name.size();
+        names.insert(names.end(), ck.name.begin(), ck.name.end());
+        grp.push_back(g);
+      }
+      grp.back().nq++;
+      qs[k] = CurQuery{q.peer, q.ctr, q.has_id};
+    }
+    dg0.push_back((uint32_t)grp.size());
+    names.resize(names.size() + 16, 0);
+    b_cur_doc.ensure(qdoc.size() * 4); b_cur_dg.ensure(dg0.size() * 4); b_cur_grp.ensure(grp.size() * sizeof(CurGroup));
+    b_cur_q.ensure(qs.size() * sizeof(CurQuery)); b_cur_names.ensure(names.size()); b_cur_res.ensure(qs.size() * sizeof(CurRes));
+    lmbe::h2d(b_cur_doc.p, qdoc.data(), qdoc.size() * 4);
+    lmbe::h2d(b_cur_dg.p, dg0.data(), dg0.size() * 4);
+    lmbe::h2d(b_cur_grp.p, grp.data(), grp.size() * sizeof(CurGroup));
+    lmbe::h2d(b_cur_q.p, qs.data(), qs.size() * sizeof(CurQuery));
+    lmbe::h2d(b_cur_names.p, names.data(), names.size());
+    Dev d = last_d;
+    std::vector<KernelTime> t;
+    lmbe::reset_times();
+    lmbe::tic(profiling);
+    LM_LAUNCH(k_cursor, qdoc.size(), 64, d, (const uint32_t*)b_cur_doc.as<uint32_t>(), (const uint32_t*)b_cur_dg.as<uint32_t>(), (const CurGroup*)b_cur_grp.as<CurGroup>(),
+              (const CurQuery*)b_cur_q.as<CurQuery>(), (const uint8_t*)b_cur_names.as<uint8_t>(), b_cur_res.as<CurRes>(), at ? 1 : 0);
+    lmbe::toc("k_cursor", t, profiling);
+    std::vector<CurRes> r(qs.size());
+    lmbe::d2h(r.data(), b_cur_res.p, r.size() * sizeof(CurRes));
+    lmbe::sync();
+    lmbe::flush_times(t);
+    for (auto& kt : t) cur_ms += kt.ms;
+    for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
   }
 
   // ---- lm_export: the updates document `i` holds beyond `from_vv` (lm_export.h).  The blobs come back from the arena, the
