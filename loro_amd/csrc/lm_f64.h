@@ -1,9 +1,16 @@
 // f64 → JSON number text, shortest digits that round-trip, laid out like serde_json / ryu's "pretty" printer
 // (what `LoroValue::to_json_value` produces for LoroValue::Double; reference: crates/loro-common/src/value.rs:719-738).
 // Digit generation is the free-format algorithm of Burger & Dybvig ("Printing Floating-Point Numbers Quickly and
-// Accurately", PLDI'96, figure 3: scale by an estimate of log10, fix up, generate) on a small fixed-width bignum:
-// integer arithmetic only, so the host build and the gfx950 build agree bit for bit.  f64 values are rare in the
-// documents this engine merges; the routine favours being obviously exact over being fast.
+// Accurately", PLDI'96, figure 3: scale by an estimate of log10, fix up, generate) on a small fixed-width bignum.
+// The digits are integer arithmetic only.  The ESTIMATE of the decimal exponent is not: it is ceil(n · log10 2 - 1e-10) in
+// `double`, n = e2 + bitlen - 1 in -1074..1023, and a compiler may contract the product and the subtraction into one fma.
+// That cannot change it: for every n != 0 of that range n · log10 2 is at least 4.5e-4 away from an integer (the closest
+// is n = ±485, ±145.9995479), the rounding of either form is below 1e-13, so both give ceil(n · log10 2) — and the
+// fix-up only corrects an estimate that is one too low.  tests/test_values.py checks the margin for all 2,098 values of n in
+// exact arithmetic, and tests/_values.py f64_corpus() holds doubles of every n (every biased exponent, every denormal
+// bit length), which the CPU build and the gfx950 build (tests/test_gpu_zz_values.py) both render against a plain
+// reference.  f64 values are rare in the documents this engine merges; the routine favours being obviously exact over
+// being fast.
 #pragma once
 #include <cstdint>
 #include "lm_wave.h"

@@ -304,7 +304,11 @@ LM_DEV uint32_t scan_incl_max(uint32_t v) {
 // ops) instead of an LDS permute; lanes below d keep their own value
 LM_DEV uint32_t shift_up(uint32_t v, int d) {
   uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xf, 0xf, false);
-  if (d == 2) t = (uint32_t)__builtin_amdgcn_update_dpp((int)t, (int)t, 0x138, 0xf, 0xf, false);
+  if (d == 2) {
+    // (the second step hands lane 1 what lane 0 kept in the first, lane 0's value: lanes 0 and 1 take their own back)
+    t = (uint32_t)__builtin_amdgcn_update_dpp((int)t, (int)t, 0x138, 0xf, 0xf, false);
+    t = lane() < 2 ? v : t;
+  }
   return t;
 }
 // same, but lanes below d receive 0: no tied `old` operand, so no register copy in front of the DPP move

@@ -447,7 +447,8 @@ def nested_map_order_docs():
     """List items and Map values that are MAPS: key order (bytewise, not insertion), keys that share their first eight bytes, keys
     that are prefixes of one another, an empty key, DUPLICATE keys inside one encoded map (the last occurrence wins — what a map
     built by successive inserts holds, value.rs read_value), a 70-entry map (beyond the 64 entries the renderer orders in one
-    pass), maps nested in maps in lists, and enough of them in one value to exhaust the renderer's pool."""
+    pass), maps nested in maps in lists, and many map frames under one value that take and return the renderer's pool slots (never more
+    than 66 at once — the exhausted pool is tests/_values.py nested())."""
     from loro_amd import wire
 
     class PairMap(dict):   # a map value whose encoded entries are exactly these pairs, duplicates included
@@ -468,7 +469,7 @@ def nested_map_order_docs():
         PairMap([(k, i) for i, k in enumerate(long)] + [("prefix__", "short"), ("prefix_", 0.5), ("prefix__a", "again")]),
         {"key%02d" % (i * 37 % 70): i for i in range(70)},
         PairMap([("m", PairMap([("y", [1, {"q": 1, "p": 2}]), ("x", PairMap([("b", 1), ("b", 2), ("a", 3)])), ("y", "last")])), ("l", [PairMap([]), {}])]),
-        [{"n%d" % j: {"i%d" % i: i for i in range(60)} for j in range(6)}],     # 6 x 60 entries under one frame: the pool runs out
+        [{"n%d" % j: {"i%d" % i: i for i in range(60)} for j in range(6)}],     # 6 x 60 entries under one frame, one after the other: each takes its slots and hands them back
         {},
     ]
     r.list_insert("list", 0, vals)
