@@ -18,18 +18,21 @@
 //      behind it (same peer, counter + 1: its End, every writer emits the pair) carries that mark;
 //   B  64 visible elements per step: the scalars between two anchors are escaped and stored by all lanes at once, an anchor
 //      opens / closes its StyleOp in the active set (LDS) and takes its mark off again; before scalars are written after a change
-//      of the set, the winners per key are worked out and compared BY VALUE (key bytes, encoded value bytes) with the open span's.
+//      of the set, the winners per key are worked out and compared BY VALUE (key bytes, decoded values: rt_value_eq) with the open span's; a span that goes on keeps the attributes it was opened with.
 // Output per document: {"<container id>":[span,…],…} for the Text containers in which something — a scalar or an anchor — is visible
 // at the rendered version; the kernel writes the members in the order of the document's container table, the host (Engine::richtext)
 // puts the members of a document that lists several into the bytewise order of their JSON-encoded keys (ContainerID Display: cid:root-<name>:Text / cid:<counter>@<peer>:Text).
-// Limits: at most RT_MAX StyleOps open at one scalar and RT_MAX distinct style keys per Text (LM_UNSUPPORTED beyond); two values are "equal" when their encodings are
-// (map-typed style values with the same entries in another order split a span the reference would merge).
+// Limits: at most RT_MAX StyleOps open at one scalar and RT_MAX distinct style keys per Text (LM_UNSUPPORTED beyond).  Two style values are
+// equal when the DECODED values are equal as the reference compares them (LoroValue's PartialEq, rt_value_eq below): never by their
+// encodings — a nested map's keys are indices into its own block's key table — and never by their JSON.
 #pragma once
 #include "lm_k_emit.h"
 
 namespace lm {
 
 static constexpr uint32_t RT_MAX = 64;
+static constexpr uint32_t RT_BLOCK = 64;   // k_richtext's workgroup: ONE wave per document.  Its LDS tables, sink_value's and rt_value_eq_walk's frame stacks are
+                                           // written by lane 0 between wave-level syncs and read by all lanes: a second wave in the group would race on them
 
 struct RtStyle { const uint8_t* kp; const uint8_t* vp; uint32_t kl, vl, lam, peer, blk; bool null; };
 
@@ -61,6 +64,160 @@ LM_DEV RtStyle rt_style(const Dev& d, const DocMeta& m, uint32_t srow, int32_t& 
   if (v.bad) err = err ? err : ST_DATA_CORRUPTION;
   s.vl = (uint32_t)(v.p - s.vp);
   return s;
+}
+
+// Are the values of two StyleOps equal as the reference compares them — LoroValue's PartialEq (loro-common/src/value.rs:29-44),
+// which get_richtext_value joins spans by (richtext_state.rs:2546-2584)?  Decided on the DECODED values: values of different kinds
+// are never equal (I64(1) != Double(1.0), a list is not a binary), doubles are equal when a == b (0.0 == -0.0) or both are NaN,
+// lists elementwise, maps as hash maps: the order of the entries does not count, of a key written twice the last value does.  The
+// keys of a nested map are indices into the key table of the value's OWN block (docs/encoding.md §10.1), so the encodings say
+// nothing across blocks: equal bytes can be different maps and equal maps different bytes.
+// Wave-uniform like sink_value: both values are walked side by side, one frame per open list / map in LDS (rem = items of A left;
+// for a map, where B's entries begin, how many there are and where B's map ends).  A is read front to back; for an entry of A
+// that no later entry shadows, the last entry of B with that key is looked up and the readers go on there — K passes over K
+// entries, like the renderer's fallback (map VALUES are small).  Equal numbers of distinct keys on both sides and every key of A
+// found in B: the key sets are equal.
+// (out of line: the walk keeps its readers and the frame stacks of skip_loro_value apart from the registers of walk B, which calls it
+// only for values that rt_value_eq below cannot decide at a glance)
+LM_DEV_NOINLINE int32_t rt_value_eq_walk(const uint8_t* data, const uint64_t* key_off, const uint32_t* key_len, const uint8_t* avp, uint32_t avl, uint32_t ka0,
+                                         uint32_t kan, const uint8_t* bvp, uint32_t bvl, uint32_t kb0, uint32_t kbn) {
+  LM_SHARED(uint32_t, s_cf, 4 * 16);   // one per workgroup, shared by the one wave that runs in it (RT_BLOCK)
+  static_assert(RT_BLOCK == 64, "the frame stack is owned by a single wave");
+  const int lane = lmw::lane();
+  auto fset = [&](int f, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3) {
+    lmw::wave_sync();
+    if (lane == 0) { s_cf[4 * f] = c0; s_cf[4 * f + 1] = c1; s_cf[4 * f + 2] = c2; s_cf[4 * f + 3] = c3; }
+    lmw::wave_sync();
+  };
+  auto key_same = [&](uint32_t ra, uint32_t rb) { return ra == rb || (key_len[ra] == key_len[rb] && bytes_eq(data + key_off[ra], data + key_off[rb], key_len[ra])); };
+  // the n entries of a map at q: how many distinct keys, q left behind the map (false: a key index beyond the table, a damaged value)
+  auto map_scan = [&](Rd& q, uint32_t n, uint32_t k0, uint32_t kn, uint32_t& distinct) -> bool {
+    distinct = 0;
+    for (uint32_t i = 0; i < n; i++) {
+      const uint64_t kidx = rd_uleb(q);
+      if (q.bad || kidx >= kn) return false;
+      bool u = false;
+      skip_loro_value(q, u);
+      Rd t = q;
+      bool shadowed = false;
+      for (uint32_t j = i + 1; j < n && !shadowed; j++) {
+        const uint64_t k2 = rd_uleb(t);
+        if (t.bad || k2 >= kn) return false;
+        shadowed = key_same(k0 + (uint32_t)kidx, k0 + (uint32_t)k2);
+        skip_loro_value(t, u);
+      }
+      if (!shadowed) distinct++;
+    }
+    return !q.bad;
+  };
+  Rd a = rd_make(avp, avl), b = rd_make(bvp, bvl);
+  uint32_t f_map = 0;   // bit i: frame i is a map
+  int sp = 0;
+  bool pending = true;  // a pair of values waits at a.p / b.p
+  for (uint32_t guard = 0; guard < (1u << 28); guard++) {
+    if (a.bad || b.bad) return -(int32_t)ST_DATA_CORRUPTION;
+    if (!pending) {
+      if (sp == 0) return 1;
+      const int top = sp - 1;
+      lmw::wave_sync();
+      const uint32_t rem = s_cf[4 * top], b_start = s_cf[4 * top + 1], b_n = s_cf[4 * top + 2], b_end = s_cf[4 * top + 3];
+      const bool is_map = (f_map >> top) & 1;
+      if (rem == 0) { if (is_map) b.p = bvp + b_end; sp--; continue; }
+      fset(top, rem - 1, b_start, b_n, b_end);
+      if (!is_map) { pending = true; continue; }
+      const uint64_t kidx = rd_uleb(a);
+      if (a.bad || kidx >= kan) return -(int32_t)ST_DATA_CORRUPTION;
+      const uint32_t krow = ka0 + (uint32_t)kidx;
+      bool u = false, shadowed = false;
+      Rd t = a;
+      skip_loro_value(t, u);
+      const uint8_t* a_next = t.p;
+      for (uint32_t j = 1; j < rem && !shadowed; j++) {
+        const uint64_t k2 = rd_uleb(t);
+        if (t.bad || k2 >= kan) return -(int32_t)ST_DATA_CORRUPTION;
+        shadowed = key_same(krow, ka0 + (uint32_t)k2);
+        skip_loro_value(t, u);
+      }
+      if (shadowed) { a.p = a_next; continue; }
+      uint32_t found = NONE;
+      t = rd_make(bvp + b_start, (uint64_t)(b_end - b_start));
+      for (uint32_t j = 0; j < b_n; j++) {
+        const uint64_t k2 = rd_uleb(t);
+        if (t.bad || k2 >= kbn) return -(int32_t)ST_DATA_CORRUPTION;
+        if (key_same(krow, kb0 + (uint32_t)k2)) found = (uint32_t)(t.p - bvp);
+        skip_loro_value(t, u);
+      }
+      if (found == NONE) return 0;
+      b.p = bvp + found;
+      pending = true;
+      continue;
+    }
+    pending = false;
+    const uint32_t tag = rd_u8(a);
+    if (tag != rd_u8(b)) return 0;   // another kind (true and false have tags of their own)
+    switch (tag) {
+      case 0: case 1: case 2: break;
+      case 3: if (rd_sleb(a) != rd_sleb(b)) return 0; break;
+      case 4: {
+        uint64_t x = 0, y = 0;
+        for (int k = 0; k < 8; k++) { x = (x << 8) | rd_u8(a); y = (y << 8) | rd_u8(b); }
+        const uint64_t mx = x & 0x7fffffffffffffffull, my = y & 0x7fffffffffffffffull, inf = 0x7ff0000000000000ull;
+        if (!(mx > inf ? my > inf : (x == y || (mx | my) == 0))) return 0;   // both NaN, or a == b: the same number, or both zeros
+        break;
+      }
+      case 5: case 6: {
+        const uint64_t la = rd_uleb(a), lb = rd_uleb(b);
+        if (la > rd_left(a) || lb > rd_left(b)) return -(int32_t)ST_DATA_CORRUPTION;
+        if (la != lb || !bytes_eq(a.p, b.p, (uint32_t)la)) return 0;
+        rd_skip(a, la); rd_skip(b, lb);
+        break;
+      }
+      case 7: case 8: {
+        const uint64_t na = rd_uleb(a), nb = rd_uleb(b);
+        if (a.bad || b.bad) break;
+        if (sp >= 16 || na > (1u << 28) || nb > (1u << 28)) return -(int32_t)ST_UNSUPPORTED;
+        if (tag == 7) {
+          if (na != nb) return 0;
+          f_map &= ~(1u << sp);
+          fset(sp, (uint32_t)na, 0, 0, 0);
+        } else {
+          uint32_t da = 0, db = 0;
+          Rd t = a;
+          if (!map_scan(t, (uint32_t)na, ka0, kan, da)) return -(int32_t)ST_DATA_CORRUPTION;
+          const uint32_t b_start = (uint32_t)(b.p - bvp);
+          t = b;
+          if (!map_scan(t, (uint32_t)nb, kb0, kbn, db)) return -(int32_t)ST_DATA_CORRUPTION;
+          if (da != db) return 0;
+          f_map |= 1u << sp;
+          fset(sp, (uint32_t)na, b_start, (uint32_t)nb, (uint32_t)(t.p - bvp));
+        }
+        sp++;
+        break;
+      }
+      case 9: if (rd_u8(a) != rd_u8(b)) return 0; break;   // (a container as a style value: the renderer refuses the span)
+      default: return -(int32_t)ST_UNSUPPORTED;
+    }
+  }
+  return -(int32_t)ST_UNSUPPORTED;
+}
+
+// ST_RT_WALK (device to host only, never a caller's status): k_richtext met two values only the walk can compare and rendered nothing
+// for this document — the host launches k_richtext_walk for the documents that carry it (lm_pipeline.h).  Two kernels because the
+// call, wherever it stands, adds scratch and register traffic to walk B of EVERY document (resource figures: DESIGN §13.6).
+static constexpr int32_t ST_RT_WALK = 0x7f000001;
+template <bool WALK>
+LM_DEV bool rt_value_eq(const Dev& d, const RtStyle& A, const RtStyle& B, int32_t& err) {
+  if (A.vl == 0 || B.vl == 0) return A.vl == B.vl;   // (a damaged value: rt_style has raised err)
+  // the same bytes read through the same key table; null / true / false, which are their tag (every bold:true, whichever block it is in)
+  if (A.blk == B.blk && A.vl == B.vl && (A.vp == B.vp || bytes_eq(A.vp, B.vp, A.vl))) return true;
+  if (*A.vp < 3 || *B.vp < 3) return *A.vp == *B.vp;
+  if (!WALK) { err = err ? err : ST_RT_WALK; return false; }
+  // (everything by value and the verdict in the result — 1 equal, 0 not, < 0 a status: a reference handed to an out-of-line callee would
+  // pin `err` and the two RtStyles, which walk B touches all the time, in scratch memory)
+  const int32_t r = rt_value_eq_walk(d.data, d.key_off, d.key_len, A.vp, A.vl, d.boff[(uint64_t)A.blk * BCN + BC_KEY], d.bcnt[(uint64_t)A.blk * BCN + BC_KEY],
+                                     B.vp, B.vl, d.boff[(uint64_t)B.blk * BCN + BC_KEY], d.bcnt[(uint64_t)B.blk * BCN + BC_KEY]);
+  if (r < 0) err = err ? err : -r;
+  return r > 0;
 }
 
 LM_DEV void sink_u64(Sink& s, uint64_t u) {
@@ -126,11 +283,13 @@ LM_DEV void rt_walk(const Dev& d, const DocMeta& m, uint32_t cidx, uint32_t vis_
   }
 }
 
-// mode 1 (the only one the host uses): write into out + out_off[doc] (capacity out_off[doc + 1] - out_off[doc]; nothing is written beyond it) and report the exact size — Engine::richtext launches once into optimistic slabs and a second time, at exact sizes, only when a document overflowed; mode 0 (sizes only) is kept for experiments.
+// mode 1 (the only one the host uses): write into out + out_off[doc] (capacity out_off[doc + 1] - out_off[doc]; nothing is written beyond it) and report the exact size — Engine::richtext launches once into optimistic slabs and a second time, at exact sizes, only when a document overflowed; mode 0 (sizes only) is kept for experiments; mode 2 (k_richtext_walk behind k_richtext): as mode 1, for the documents whose rt_status is ST_RT_WALK only — the others keep what k_richtext wrote.
 // rt_len[doc] = the exact size either way
-LM_KERNEL void k_richtext(Dev d, uint8_t* out, const uint64_t* out_off, uint32_t* rt_len, int32_t* rt_status, uint32_t* rt_cnt, int mode) {
+template <bool WALK>
+LM_DEV void richtext_doc(const Dev& d, uint8_t* out, const uint64_t* out_off, uint32_t* rt_len, int32_t* rt_status, uint32_t* rt_cnt, int mode) {
   const uint32_t doc = (uint32_t)lmw::bid();
   const int lane = lmw::lane();
+  if (WALK && mode == 2 && rt_status[doc] != ST_RT_WALK) return;   // (wave-uniform: one wave per document)
   const DocMeta m = d.doc[doc];
   if (status_fatal(m.status)) { if (lane == 0) { rt_len[doc] = 0; rt_status[doc] = m.status; rt_cnt[doc] = 0; } return; }
   const uint32_t C = m.n_cont;
@@ -217,7 +376,7 @@ LM_KERNEL void k_richtext(Dev d, uint8_t* out, const uint64_t* out_off, uint32_t
         const RtStyle A = rt_style(d, m, w, err);
         for (uint32_t j = 0; j < n_open && !hit; j++) {
           const RtStyle B = rt_style(d, m, s_open[j], err);
-          hit = A.kl == B.kl && A.vl == B.vl && bytes_eq(A.kp, B.kp, A.kl) && bytes_eq(A.vp, B.vp, A.vl);
+          hit = A.kl == B.kl && bytes_eq(A.kp, B.kp, A.kl) && rt_value_eq<WALK>(d, A, B, err);
         }
         if (!hit) return false;
       }
@@ -346,6 +505,15 @@ LM_KERNEL void k_richtext(Dev d, uint8_t* out, const uint64_t* out_off, uint32_t
     rt_cnt[doc] = n_listed;
     rt_status[doc] = err ? err : (int32_t)ST_OK;   // (s.pos > s.cap: the host sees the size and launches again with room for it)
   }
+}
+
+// k_richtext: every document whose style values compare at a glance (rt_value_eq) — a document that needs the walk comes back with
+// ST_RT_WALK and nothing rendered; k_richtext_walk: the same body with the walk in it (mode 2: for those documents only)
+LM_KERNEL void k_richtext(Dev d, uint8_t* out, const uint64_t* out_off, uint32_t* rt_len, int32_t* rt_status, uint32_t* rt_cnt, int mode) {
+  richtext_doc<false>(d, out, out_off, rt_len, rt_status, rt_cnt, mode);
+}
+LM_KERNEL void k_richtext_walk(Dev d, uint8_t* out, const uint64_t* out_off, uint32_t* rt_len, int32_t* rt_status, uint32_t* rt_cnt, int mode) {
+  richtext_doc<true>(d, out, out_off, rt_len, rt_status, rt_cnt, mode);
 }
 
 }  // namespace lm

@@ -126,7 +126,7 @@ struct Engine {
   std::vector<uint32_t> h_rt_len;
   std::vector<int32_t> h_rt_status;
   bool rt_ran = false;
-  int rt_launches = 0;                            // k_richtext launches of the last lm_richtext (2: a slab was too small)
+  int rt_launches = 0;                            // k_richtext / k_richtext_walk launches of the last lm_richtext (1; + 1: style values that need the walk; + 1: a slab was too small)
   // lm_cursor_pos / lm_cursor_at (lm_k_cursor.h)
   DBuf b_cur_doc, b_cur_dg, b_cur_grp, b_cur_q, b_cur_names, b_cur_res;
   bool keep_tombstones = false;                   // the next runs replay without the linear prefix (it drops what it deletes from the leaves: cursor_needs_tombstones)
@@ -1616,7 +1616,8 @@ struct Engine {
   // of k_richtext into optimistic slabs (twice the document's JSON + a few KB: a span costs ~40 bytes on top of its text); the kernel
   // never writes beyond a slab and always reports the exact size, so a document that needs more sends the batch through a second
   // launch at exact sizes (as the JSON renderer's DF_REEMIT does).  LM_RT_SLAB=<bytes> overrides the slab size (tests: 0 forces the
-  // second launch).
+  // second launch).  k_richtext decides the equality of two style values at a glance or not at all: the documents it leaves with
+  // ST_RT_WALK (a number, string, list or map against another op's) are rendered by one launch of k_richtext_walk in between.
   void richtext() {
     lmbe::bind(sc);
     if (!ran) throw std::runtime_error("lm_richtext before lm_run");
@@ -1639,22 +1640,33 @@ struct Engine {
       uint64_t cap = h_doc[i].status == ST_OK ? (slab_env ? (uint64_t)atoll(slab_env) : 2ull * h_doc[i].out_len + 64ull * h_doc[i].n_cont + 4096) : 0;
       h_rt_off[i + 1] = h_rt_off[i] + ((cap + 15) & ~15ull);
     }
-    for (int attempt = 0; attempt < 2; attempt++) {
+    // one launch into the slabs of h_rt_off and the sizes, member counts and statuses back.  mode 1: every document; mode 2:
+    // k_richtext_walk for the documents that k_richtext left with ST_RT_WALK (their style values need rt_value_eq_walk), the others
+    // keep what they have
+    auto pass = [&](bool walk, int mode) {
       b_rt_out.ensure(h_rt_off[n_docs] + 64);
       b_rt_off.ensure((size_t)(n_docs + 1) * 8);
       lmbe::h2d(b_rt_off.p, h_rt_off.data(), (size_t)(n_docs + 1) * 8);
-      LM_LAUNCH(k_richtext, n_docs, 64, d, b_rt_out.as<uint8_t>(), (const uint64_t*)b_rt_off.as<uint64_t>(), len, st, cnt, 1);
+      if (walk) LM_LAUNCH(k_richtext_walk, n_docs, RT_BLOCK, d, b_rt_out.as<uint8_t>(), (const uint64_t*)b_rt_off.as<uint64_t>(), len, st, cnt, mode);
+      else LM_LAUNCH(k_richtext, n_docs, RT_BLOCK, d, b_rt_out.as<uint8_t>(), (const uint64_t*)b_rt_off.as<uint64_t>(), len, st, cnt, mode);
       rt_launches++;
       lmbe::d2h(h_rt_len.data(), len, (size_t)n_docs * 4);
       lmbe::d2h(h_cnt.data(), cnt, (size_t)n_docs * 4);
       lmbe::d2h(h_rt_status.data(), st, (size_t)n_docs * 4);
       lmbe::sync();
-      bool over = false;
-      for (uint32_t i = 0; i < n_docs; i++) over |= h_rt_status[i] == ST_OK && h_rt_len[i] > h_rt_off[i + 1] - h_rt_off[i];
-      if (!over) break;
-      if (attempt == 1) { for (uint32_t i = 0; i < n_docs; i++) if (h_rt_status[i] == ST_OK && h_rt_len[i] > h_rt_off[i + 1] - h_rt_off[i]) h_rt_status[i] = ST_INTERNAL; break; }
+    };
+    auto over = [&](uint32_t i) { return h_rt_status[i] == ST_OK && h_rt_len[i] > h_rt_off[i + 1] - h_rt_off[i]; };
+    pass(false, 1);
+    bool walk = false, any_over = false;
+    for (uint32_t i = 0; i < n_docs; i++) walk |= h_rt_status[i] == ST_RT_WALK;
+    if (walk) pass(true, 2);   // (the same slabs)
+    for (uint32_t i = 0; i < n_docs; i++) any_over |= over(i);
+    if (any_over) {   // a slab was too small: every document once more at exact sizes, by the kernel the batch needs
       for (uint32_t i = 0; i < n_docs; i++) h_rt_off[i + 1] = h_rt_off[i] + (h_rt_status[i] == ST_OK ? ((uint64_t)h_rt_len[i] + 15) & ~15ull : 0);
+      pass(walk, 1);
+      for (uint32_t i = 0; i < n_docs; i++) if (over(i)) h_rt_status[i] = ST_INTERNAL;
     }
+    for (uint32_t i = 0; i < n_docs; i++) if (h_rt_status[i] == ST_RT_WALK) h_rt_status[i] = ST_INTERNAL;   // (k_richtext_walk never reports it)
     h_rt.resize(h_rt_off[n_docs] + 1);
     if (h_rt_off[n_docs]) lmbe::d2h(h_rt.data(), b_rt_out.p, h_rt_off[n_docs]);
     lmbe::sync();

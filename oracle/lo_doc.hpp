@@ -92,6 +92,35 @@ inline void json_f64(double v, std::string& out) {
 struct Doc;
 inline void json_value(const Doc& d, const Value& v, std::string& out, int depth);
 
+// LoroValue's PartialEq (loro-common/src/value.rs:29-44): values of different kinds are never equal (I64(1) != Double(1.0)), doubles
+// are equal when a == b (so 0.0 == -0.0) or both are NaN, lists elementwise, maps as hash maps — whatever the order of their entries,
+// of a key written twice the last value counts
+inline bool value_eq(const Value& a, const Value& b) {
+  if (a.kind != b.kind) return false;
+  switch (a.kind) {
+    case V_NULL: return true;
+    case V_BOOL: return a.b == b.b;
+    case V_I64: return a.i == b.i;
+    case V_F64: return a.f == b.f || (std::isnan(a.f) && std::isnan(b.f));
+    case V_STR: case V_BIN: return a.s == b.s;
+    case V_LIST: {
+      if (a.list.size() != b.list.size()) return false;
+      for (size_t i = 0; i < a.list.size(); i++) if (!value_eq(a.list[i], b.list[i])) return false;
+      return true;
+    }
+    case V_MAP: {
+      std::map<std::string, const Value*> ma, mb;
+      for (auto& e : a.map) ma[e.first] = &e.second;
+      for (auto& e : b.map) mb[e.first] = &e.second;
+      if (ma.size() != mb.size()) return false;
+      for (auto ia = ma.begin(), ib = mb.begin(); ia != ma.end(); ++ia, ++ib)
+        if (ia->first != ib->first || !value_eq(*ia->second, *ib->second)) return false;
+      return true;
+    }
+    default: return a.cid == b.cid;
+  }
+}
+
 // ---------------------------------------------------------------- document
 struct StyleRec { PeerID peer; Counter cnt; uint32_t end; };
 // a style anchor as the richtext state keeps it (RichtextStateChunk::Style { style: Arc<StyleOp>, anchor_type },
@@ -683,17 +712,30 @@ struct Doc {
         }
     seq_pos = 0;
     std::vector<const AnchorRec*> active;
+    typedef std::map<std::string, const AnchorRec*> Winners;   // the deciding op of every key that has a value
+    Winners open_win;
     std::string open_attr, cur_text;
     bool span_open = false, first = true;
-    auto attrs_now = [&]() {
-      std::map<std::string, const AnchorRec*> win;
+    auto winners_now = [&]() {
+      Winners win;
       for (const AnchorRec* a : active) {
         auto w = win.find(a->key);
         if (w == win.end() || w->second->lamport < a->lamport || (w->second->lamport == a->lamport && w->second->peer < a->peer)) win[a->key] = a;
       }
+      for (auto w = win.begin(); w != win.end();) w = w->second->value.kind == V_NULL ? win.erase(w) : std::next(w);
+      return win;
+    };
+    // neighbouring spans are one span iff their attribute maps are equal as LoroValues (richtext_state.rs:2546-2584 `&attributes ==
+    // last`, value_eq below) — not iff they print alike: inf, -inf and NaN all print null, 0.0 and -0.0 do not print alike
+    auto same_attrs = [](const Winners& a, const Winners& b) {
+      if (a.size() != b.size()) return false;
+      for (auto ia = a.begin(), ib = b.begin(); ia != a.end(); ++ia, ++ib)
+        if (ia->first != ib->first || !value_eq(ia->second->value, ib->second->value)) return false;
+      return true;
+    };
+    auto attrs_json = [&](const Winners& win) {
       std::string o;
       for (auto& kv : win) {
-        if (kv.second->value.kind == V_NULL) continue;
         o.push_back(o.empty() ? '{' : ',');
         json_escape(kv.first, o);
         o.push_back(':');
@@ -721,9 +763,9 @@ struct Doc {
           if ((uint64_t)ci >= st.cps.size()) fail(ST_DATA_CORRUPTION, "visible span without content");
           uint32_t cp = st.cps[ci];
           if (cp != 0xFFFFFFFFu) {
-            std::string a = attrs_now();
-            if (span_open && a != open_attr) close_span();
-            if (!span_open) { span_open = true; open_attr = a; }
+            Winners w = winners_now();
+            if (span_open && !same_attrs(w, open_win)) close_span();
+            if (!span_open) { span_open = true; open_attr = attrs_json(w); open_win = std::move(w); }   // (a joined span keeps the first one's attributes)
             cp_to_utf8(cp, cur_text);
             continue;
           }

@@ -5,7 +5,7 @@ import json
 
 import pytest
 
-import _emu, _oracle, _richtext
+import _emu, _fuzz, _oracle, _richtext, _richtext_ref
 from loro_amd._cabi import Context
 
 
@@ -142,3 +142,96 @@ def test_damaged_mixed_documents(monkeypatch, seed, auto):
     monkeypatch.setenv("LM_SPAN_AUTO", auto)
     n_both, _ = _richtext.check_damaged(_harness, _richtext.damaged_mixed_docs(600, seed=seed))
     assert n_both >= 40
+
+
+# ---- spans joined by VALUE: the oracle and the harness against the plain reference (tests/_richtext_ref.py)
+def _session_orders(reps):
+    """cid -> visible ids of every Text the replicas wrote, from the merged history (ordering has tests of its own)"""
+    from loro_amd import wire
+    blobs = _fuzz.blobs_of(reps)
+    cids = {op.cid for c in _richtext_ref.changes_of(reps) for op in c.ops if op.cid.kind == wire.KIND_TEXT}
+    return blobs, {cid: _oracle.visible_ids(blobs, cid, wire.KIND_TEXT) for cid in cids}
+
+
+def test_value_pairs_are_what_the_reference_rule_says():
+    pairs = _richtext.value_pairs()
+    assert sum(1 for p in pairs if p[3]) == 11 and sum(1 for p in pairs if not p[3]) == 16
+
+
+def test_oracle_against_the_plain_reference_on_the_value_corpus():
+    cases = _richtext.value_corpus()
+    assert len(cases) > 900
+    _richtext.check_cases(_oracle.richtext_batch([c.blobs for c in cases]), cases, "oracle")
+    # the corpus decides by value: in the touching placement an equal pair is ONE span showing the first value, an unequal pair two
+    for name, v1, v2, eq in _richtext.value_pairs():
+        for a, b in ((v1, v2), (v2, v1)):
+            sp = _richtext_ref.spans(*(lambda c: (c.changes, _richtext.TEXT, c.order))(_richtext.placements(a, b)[0]))
+            assert len(sp) == (1 if eq else 2) and sp[0][0]["c"] is a, name
+
+
+def test_oracle_against_the_plain_reference_on_the_existing_corpora():
+    """a third opinion on what the device is already compared with the oracle on: the rich fuzz sessions, the hand cases (deleted
+    Start / End anchors, concurrent marks of one key, an unmark over part of a range, a Text that holds only anchors), the nested sessions"""
+    sessions = [("fuzz %d" % i, r) for i, r in enumerate(_richtext.fuzz_sessions(30))] + _richtext.hand_sessions()
+    sessions += [("nested %d" % i, r) for i, r in enumerate(_richtext.nested_sessions(6))]
+    docs = _richtext.fuzz_docs(30) + [b for _, b in _richtext.hand_cases()] + _richtext.nested_docs(6)
+    got = _oracle.richtext_batch(docs)
+    for (name, reps), (st, js) in zip(sessions, got):
+        _, orders = _session_orders(reps)
+        assert st == 0 and js == _richtext_ref.richtext_bytes(_richtext_ref.changes_of(reps), orders), (name, js[:300])
+    assert sum(js.count(b'"attributes"') for _, js in got) > 50
+
+
+@pytest.mark.parametrize("span", ["1", "0"])
+def test_harness_against_the_plain_reference(monkeypatch, span):
+    monkeypatch.setenv("LM_SPAN", span)
+    cases = _richtext.value_corpus()
+    _, got = _harness([c.blobs for c in cases])
+    _richtext.check_cases(got, cases, "span=" + span)
+
+
+def test_harness_on_the_rows_the_corpus_was_asked_for():
+    """abc marked c=v1, def c=v2: same bytes that are different maps (two spans, the second with ITS value), maps in another key order,
+    two NaNs and the two zeros (one span), the infinities and NaN (two, although all print null), 1 and 1.0 (two)"""
+    for row, cases in _richtext.table_rows():
+        _, got = _harness([c.blobs for c in cases])
+        _richtext.check_cases(got, cases, row)
+        _richtext.check_cases(_oracle.richtext_batch([c.blobs for c in cases]), cases, "oracle " + row)
+
+
+def test_harness_on_the_rows_when_no_slab_fits(monkeypatch):
+    """three launches: k_richtext leaves the documents whose values need the walk, k_richtext_walk renders those, and because nothing
+    fits into 16 bytes the whole batch — documents of both kinds — is rendered again at exact sizes"""
+    monkeypatch.setenv("LM_RT_SLAB", "16")
+    cases = [c for _, cs in _richtext.table_rows() for c in cs] + [c for n, c, _ in _richtext.limit_cases() if n.startswith("neighbour")][:1]
+    _, got = _harness([c.blobs for c in cases])
+    _richtext.check_cases(got, cases, "slab 16")
+
+
+def test_harness_at_every_recorded_version_of_the_value_corpus():
+    cases = _richtext.value_corpus()
+    docs = _richtext.checkout_docs(cases)
+    res, got = _harness([d[2] for d in docs], [d[3] for d in docs])
+    assert all(r[0] == 0 for r in res)
+    bad = [(cases[i].name, k, g) for (i, k, _, _), g in zip(docs, got) if g != (0, cases[i].want_at(k))]
+    assert not bad, (len(bad), bad[:3])
+
+
+def test_harness_when_the_second_mark_arrives_in_a_later_import():
+    cases, sessions = _richtext.step_sessions(_richtext.value_corpus())
+    assert len(cases) > 900
+    with Context(_emu.binding()) as c:
+        got = _richtext.run_resident(c, sessions)
+    assert all(x[0] == 0 for step in got for x in step)
+    bad = [(c.name, g) for c, g in zip(cases, got[0]) if (g[1], g[2]) != (0, c.want_at(0))]
+    bad += [(c.name, g) for c, g in zip(cases, got[1]) if (g[1], g[2]) != (0, c.want)]
+    assert not bad, (len(bad), bad[:3])
+
+
+def test_harness_at_the_limits_of_the_style_tables():
+    lim = _richtext.limit_cases()
+    res, got = _harness([c.blobs for _, c, _ in lim])
+    assert [r[0] for r in res] == [0] * len(lim)       # the documents themselves are fine: the limit is the rich-text result's alone
+    assert [n for n, _, ok in lim if not ok] == ["65 open at one scalar", "65 distinct keys"]
+    for (name, c, ok), g in zip(lim, got):
+        assert g == (0, c.want) if ok else g[0] == 4, (name, g[0], g[1][:200])

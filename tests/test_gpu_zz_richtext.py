@@ -127,3 +127,68 @@ def test_damaged_change_meta_columns_are_data_corruption_like_the_reference(engi
         monkeypatch.setenv("LM_DECODE", dec)
         got = engine.merge_batch(docs)
         assert [g[0] for g in got] == [3] * len(docs), (dec, list(zip(names, [g[0] for g in got])))
+
+
+# ---- spans joined by VALUE (richtext_state.rs:2546-2584, value.rs:29-44): the device against the plain reference (tests/_richtext_ref.py,
+# no oracle or decoder code) and the oracle, on documents where two style values alone decide whether two ranges are one span
+@pytest.fixture(scope="module")
+def value_corpus():
+    cases = _richtext.value_corpus()
+    want = _oracle.richtext_batch([c.blobs for c in cases])
+    _richtext.check_cases(want, cases, "oracle")
+    return cases
+
+
+@pytest.mark.parametrize("env", [("LM_SPAN", "1"), ("LM_SPAN", "0"), ("LM_SPAN_AUTO", "1")])
+def test_value_corpus_against_the_plain_reference(engine, monkeypatch, value_corpus, env):
+    monkeypatch.setenv(*env)
+    res, got = _run(engine, [c.blobs for c in value_corpus])
+    assert all(r[0] == 0 for r in res)
+    _richtext.check_cases(got, value_corpus, "%s=%s" % env)
+
+
+def test_the_rows_the_value_corpus_was_asked_for(engine):
+    """abc marked c=v1, def c=v2: same bytes that are different maps (two spans, the second with ITS value), maps in another key order,
+    two NaNs and the two zeros (one span), the infinities and NaN (two, although all print null), 1 and 1.0 (two)"""
+    for row, cases in _richtext.table_rows():
+        _, got = _run(engine, [c.blobs for c in cases])
+        _richtext.check_cases(got, cases, row)
+
+
+def test_the_rows_when_no_slab_fits(engine, monkeypatch):
+    """three launches: k_richtext leaves the documents whose values need the walk, k_richtext_walk renders those, and because nothing
+    fits into 16 bytes the whole batch — documents of both kinds — is rendered again at exact sizes"""
+    monkeypatch.setenv("LM_RT_SLAB", "16")
+    cases = [c for _, cs in _richtext.table_rows() for c in cs] + [c for n, c, _ in _richtext.limit_cases() if n.startswith("neighbour")][:1]
+    _, got = _run(engine, [c.blobs for c in cases])
+    _richtext.check_cases(got, cases, "slab 16")
+
+
+def test_value_corpus_at_every_recorded_version(engine, monkeypatch, value_corpus):
+    monkeypatch.setenv("LM_SHARE_REPLAY", "0")
+    docs = _richtext.checkout_docs(value_corpus)
+    res, got = _run(engine, [d[2] for d in docs], [d[3] for d in docs])
+    assert all(r[0] == 0 for r in res)
+    bad = [(value_corpus[i].name, k, g) for (i, k, _, _), g in zip(docs, got) if g != (0, value_corpus[i].want_at(k))]
+    assert not bad, (len(bad), bad[:3])
+
+
+def test_value_corpus_when_the_second_mark_arrives_in_a_later_import(engine, value_corpus):
+    cases, sessions = _richtext.step_sessions(value_corpus)
+    assert len(cases) > 900
+    got = _richtext.run_resident(engine, sessions)
+    assert all(x[0] == 0 for step in got for x in step)
+    bad = [(c.name, g) for c, g in zip(cases, got[0]) if (g[1], g[2]) != (0, c.want_at(0))]
+    bad += [(c.name, g) for c, g in zip(cases, got[1]) if (g[1], g[2]) != (0, c.want)]
+    assert not bad, (len(bad), bad[:3])
+
+
+def test_the_limits_of_the_style_tables(engine):
+    """RT_MAX = 64: 63 and 64 StyleOps open at one scalar render, 65 are LM_UNSUPPORTED for that document's rich-text status only; 64
+    distinct style keys over one Text render, 65 do not; the neighbours in the batch are rendered"""
+    lim = _richtext.limit_cases()
+    res, got = _run(engine, [c.blobs for _, c, _ in lim])
+    assert [r[0] for r in res] == [0] * len(lim)
+    assert [n for n, _, ok in lim if not ok] == ["65 open at one scalar", "65 distinct keys"]
+    for (name, c, ok), g in zip(lim, got):
+        assert g == (0, c.want) if ok else g[0] == 4, (name, g[0], g[1][:200])
