@@ -350,6 +350,58 @@ typedef struct lm_cursor_at_result {
 int lm_cursor_pos(lm_ctx* ctx, const lm_cursor_query* queries, size_t n, lm_cursor_result* out);
 int lm_cursor_at(lm_ctx* ctx, const lm_cursor_at_query* queries, size_t n, lm_cursor_at_result* out);
 
+/* ---- Text and List deltas between two versions: what changed since the version this subscriber has?  LoroDoc::diff(a, b) and the
+ * TextDelta / ListDiffItem events of subscribe, answered on the device from the trackers and the decoded op rows the run left
+ * (k_delta_mark, k_delta: loro_amd/csrc/lm_k_delta.h) instead of a fetch of the whole JSON and a string diff on the host — which
+ * cannot even tell which of two equal characters was deleted.  Valid after lm_run; a query answers from A = from_vv to V = THE
+ * VERSION THAT RUN RENDERED (the latest version, the entry's checkout, a resident document's state after the last lm_import +
+ * lm_run).  Several queries may name the same document: subscribers stand at different versions.
+ *
+ * Definition, by id sets (exact, and independent of how the tracker got where it stands: A may be any version V contains).  For
+ * one Text or List container take its elements in the tracker's sequence order, which does not depend on the version:
+ *   - an element (p, c) is in A iff c < A[p] and no delete atom whose own id lies in A targets it;
+ *   - it is in V iff it is visible at the rendered version;
+ *   - style anchors are never elements of a delta;
+ *   - K = in both, I = in V only, D = in A only, everything else is skipped.
+ * Canonical delta of a container: a maximal run of K gives {"retain":n}; the I and D elements between two K runs (or a container
+ * edge), however interleaved, give at most one {"insert":...} holding all I of the gap in sequence order, followed by at most one
+ * {"delete":n} counting its D; a trailing retain is dropped; an empty delta leaves the container out.
+ * Payloads: a Text insert is a JSON string escaped exactly as lm_fetch's JSON escapes Text values; a List insert is a JSON array of
+ * the elements' values in the same canonical form; an element that is a child container is the JSON string of the parrot prefix
+ * U+1F99C ':' + its ContainerID Display (LoroValue::Container, loro-common/src/value.rs:717) — the child's content is never
+ * inlined, its delta stands under its own key.  With units == 1 a Text retain / delete counts one more per scalar >= U+10000.
+ * Result bytes of a query: one JSON object {"<ContainerID Display>":[op,...],...} over every Text / List container of the document
+ * whose delta is not empty, members in the bytewise order of their JSON-encoded keys (lm_richtext_result's rule); {} when nothing
+ * changed.  Attributes are out of scope: lm_richtext gives the styles at V.
+ *
+ * Statuses: LM_FRONTIERS_NOT_FOUND — some A[p] > V[p], or A names a peer the document does not know with a counter > 0;
+ * LM_UNSUPPORTED — the document has no rendering (an engine limit), or the kernel's self-check failed ("visible by status" must
+ * equal "c < V[p] and not deleted by an id in V" for every element; a mismatch is a delete applied by position, a damaged document
+ * or anything not thought of): the right value or a refusal, never a guess.  Returns 0, or -1 (lm_last_error) for a call that
+ * cannot be answered at all: before lm_run, during a run in flight, a document index beyond the batch, units outside 0..1.
+ * Batch shapes are the cursor calls' (folded batches are unfolded, state-staged snapshots staged once more through their history,
+ * side-engine documents answered there, a batch with a document that went through the linear prefix run once more keeping its
+ * tombstones).  Only the bytes a query's answer holds cross to the host (lm_delta_bytes).  The call changes nothing a run wrote: lm_fetch / lm_result_meta give the same bytes afterwards. */
+typedef struct lm_delta_query {
+  size_t doc;               /* index into the batch staged last */
+  const uint8_t* from_vv;   /* VersionVector::encode() bytes — what lm_fetch returned as `vv` at the earlier step, the same
+                               format lm_export takes; NULL / 0 = the empty version */
+  size_t from_vv_len;
+} lm_delta_query;
+typedef struct lm_delta_result {
+  int32_t status;           /* LM_OK | the document's import error | LM_DECODE_ERROR (from_vv is not a VersionVector) |
+                               LM_FRONTIERS_NOT_FOUND (from_vv is not contained in the rendered version) | LM_UNSUPPORTED */
+  uint32_t other_changed;   /* 1: a container of a kind this call does not cover (Map, MovableList, Tree, Counter) received an op
+                               whose id lies in V \ A — the host falls back to the rendering for those */
+  const uint8_t* json;      /* valid until the next lm_delta / lm_stage / lm_destroy */
+  size_t json_len;
+} lm_delta_result;
+/* units: 0 = Text counts in Unicode scalars, 1 = in UTF-16 code units (List counts are elements either way) */
+int lm_delta(lm_ctx* ctx, const lm_delta_query* queries, size_t n, int units, lm_delta_result* out);
+/* Bytes the last lm_delta copied from the device to the host: 16 bytes of result row per query and launch, plus the queries' JSON
+ * packed on the device (each rounded up to 16 bytes) — proportional to the change, never to the documents. */
+uint64_t lm_delta_bytes(lm_ctx* ctx);
+
 /* Wave-primitive self test on the device (DPP scan, ballot ranks); returns the number of mismatches. */
 int lm_selftest(lm_ctx* ctx);
 

@@ -37,12 +37,20 @@ class CursorAtResult(ctypes.Structure):
                 ("origin_pos", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class DeltaQuery(ctypes.Structure):
+    _fields_ = [("doc", ctypes.c_size_t), ("from_vv", ctypes.c_char_p), ("from_vv_len", ctypes.c_size_t)]
+
+
+class DeltaResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("other_changed", ctypes.c_uint32), ("json", ctypes.c_void_p), ("json_len", ctypes.c_size_t)]
+
+
 CURSOR_OK, CURSOR_DELETED, CURSOR_ID_NOT_FOUND, CURSOR_CONTAINER_NOT_FOUND, CURSOR_DOC_FAILED, CURSOR_UNSUPPORTED = range(6)
 
 SYMBOLS = ["create", "destroy", "last_error", "merge_batch", "stage", "run", "fetch", "get_stats", "set_profiling", "kernel_time", "selftest", "result_meta", "result_hashes", "n_streams", "run_async", "wait",
            "encode_block", "encode_updates", "free_bytes", "import", "resident_fresh", "import_modes", "import_lca", "export", "comm_unique_id", "comm_init", "summary_allgather",
            "summary_layout", "summary_rows_device", "summary_allgather_device", "shared_documents", "richtext", "richtext_result", "fused_documents", "redo_documents", "state_documents", "host_alloc", "host_free", "staged_direct",
-           "cursor_pos", "cursor_at"]
+           "cursor_pos", "cursor_at", "delta", "delta_bytes"]
 
 
 class Binding:
@@ -83,6 +91,9 @@ class Binding:
         self.cursor_pos.argtypes = [ctypes.c_void_p, ctypes.POINTER(CursorQuery), ctypes.c_size_t, ctypes.POINTER(CursorResult)]
         self.cursor_at = g("cursor_at"); self.cursor_at.restype = ctypes.c_int
         self.cursor_at.argtypes = [ctypes.c_void_p, ctypes.POINTER(CursorAtQuery), ctypes.c_size_t, ctypes.POINTER(CursorAtResult)]
+        self.delta = g("delta"); self.delta.restype = ctypes.c_int
+        self.delta.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeltaQuery), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(DeltaResult)]
+        self.delta_bytes = g("delta_bytes"); self.delta_bytes.restype = ctypes.c_uint64; self.delta_bytes.argtypes = [ctypes.c_void_p]
         self.comm_unique_id = g("comm_unique_id"); self.comm_unique_id.restype = ctypes.c_int; self.comm_unique_id.argtypes = [ctypes.c_char_p]
         self.comm_init = g("comm_init"); self.comm_init.restype = ctypes.c_int; self.comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
         self.summary_allgather = g("summary_allgather"); self.summary_allgather.restype = ctypes.c_long
@@ -296,6 +307,21 @@ class Context:
         if self.b.cursor_at(self.h, qs, n, out) != 0:
             raise RuntimeError(self.b.last_error(self.h).decode())
         return [(out[k].status, (out[k].peer, out[k].counter) if out[k].has_id else None, out[k].side, out[k].origin_pos) for k in range(n)]
+
+    def delta(self, queries, units=0):
+        """lm_delta (LoroDoc::diff / the TextDelta and ListDiffItem events): the Text / List deltas from a version to the version the
+        last run rendered.  queries: [(doc, from_vv)] — from_vv = VersionVector::encode bytes (what fetch() returned as `vv` at the
+        earlier step) or None for the empty version; units 0: Text counts in Unicode scalars, 1: in UTF-16 code units.
+        Returns [(status, other_changed, json bytes)].  self.b.delta_bytes(self.h) = the bytes the call copied back from the device."""
+        n = len(queries)
+        qs, out, keep = (DeltaQuery * max(n, 1))(), (DeltaResult * max(n, 1))(), []
+        for k, (doc, vv) in enumerate(queries):
+            vv = None if vv is None else bytes(vv)
+            keep.append(vv)
+            qs[k].doc = doc; qs[k].from_vv = vv; qs[k].from_vv_len = len(vv) if vv else 0
+        if self.b.delta(self.h, qs, n, units, out) != 0:
+            raise RuntimeError(self.b.last_error(self.h).decode())
+        return [(out[k].status, out[k].other_changed, ctypes.string_at(out[k].json, out[k].json_len) if out[k].json_len else b"") for k in range(n)]
 
     def comm_init(self, rank=0, world=1, unique_id=None):
         if self.b.comm_init(self.h, rank, world, unique_id or bytes(128)) != 0:

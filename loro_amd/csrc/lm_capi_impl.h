@@ -295,6 +295,7 @@ struct lm_ctx_impl {
     rd.on = false;
     sum_rows_padded = 0;             // (a new batch: lm_summary_layout is called again for it)
     for (auto& pt : parts) { pt->sum_rows = nullptr; pt->keep_tombstones = false; }
+    dl_json.clear();
     // split into contiguous ranges of about equal blob bytes; small batches stay in one part
     uint64_t total = 0;
     for (size_t i = 0; i < n; i++) for (size_t b = 0; b < docs[i].n; b++) total += docs[i].lens[b];
@@ -481,9 +482,9 @@ struct lm_ctx_impl {
   // entry's version), documents replayed in the side engine are answered there.  One more: a batch whose documents may have gone
   // through the linear prefix is run again without it (Engine::cursor_needs_tombstones).  The results of lm_fetch / lm_result_meta
   // are that run's from here on — the same bytes.
-  void cursor_prepare() {
-    if (!ran) throw std::runtime_error("lm_cursor_pos / lm_cursor_at before lm_run");
-    if (in_flight) throw std::runtime_error("lm_cursor_pos / lm_cursor_at while a run is in flight");
+  void cursor_prepare(const char* who = "lm_cursor_pos / lm_cursor_at") {
+    if (!ran) throw std::runtime_error(std::string(who) + " before lm_run");
+    if (in_flight) throw std::runtime_error(std::string(who) + " while a run is in flight");
     bool any = false;
     for (uint32_t p = 0; p < n_parts(); p++) if (parts[p]->n_state_docs && !parts[p]->resident) { parts[p]->restage_history(); any = true; }
     if (!sh.on) for (uint32_t p = 0; p < n_parts(); p++) if (parts[p]->cursor_needs_tombstones()) { parts[p]->keep_tombstones = true; any = true; }
@@ -558,6 +559,38 @@ struct lm_ctx_impl {
       e.cursor(keys, sub, r, at);
       for (size_t j = 0; j < of[p].size(); j++) out[of[p][j]] = r[j];
       if (profiling) times.push_back(lm::KernelTime{"k_cursor", e.cur_ms});
+    }
+  }
+
+  // ---- lm_delta (lm_k_delta.h): the batch shapes are the cursor calls' (cursor_prepare); the queries are routed to the engines
+  // that hold their documents as cursor() routes them
+  uint64_t dl_d2h_bytes = 0;                   // … and the bytes that call copied back from the device (result rows + packed JSON)
+  std::vector<std::vector<uint8_t>> dl_json;   // the bytes of the last lm_delta's results: valid until the next lm_delta / lm_stage / lm_destroy
+  void delta(std::vector<lm::Engine::DeltaIn>& in, int units, std::vector<lm::Engine::DeltaOut>& out) {
+    cursor_prepare("lm_delta");
+    out.assign(in.size(), lm::Engine::DeltaOut());
+    std::vector<std::vector<uint32_t>> of(n_parts() + 1);   // the queries of every part; the last list is the side engine's
+    for (size_t k = 0; k < in.size(); k++) {
+      const size_t doc = in[k].doc;
+      if (redone(doc)) { in[k].doc = (uint32_t)rd.of[doc]; of[n_parts()].push_back((uint32_t)k); continue; }
+      uint32_t p = 0;
+      if (mapped) { p = emap[doc].first; in[k].doc = emap[doc].second; }
+      else { while (p + 1 < n_parts() && doc >= first[p + 1]) p++; in[k].doc = (uint32_t)(doc - first[p]); }
+      of[p].push_back((uint32_t)k);
+    }
+    std::vector<lm::Engine::DeltaIn> sub;
+    std::vector<lm::Engine::DeltaOut> r;
+    dl_d2h_bytes = 0;
+    for (uint32_t p = 0; p <= n_parts(); p++) {
+      if (of[p].empty()) continue;
+      lm::Engine& e = p < n_parts() ? *parts[p] : *rd.eng;
+      e.profiling = profiling != 0;
+      sub.clear();
+      for (uint32_t k : of[p]) sub.push_back(in[k]);
+      e.delta(sub, units, r);
+      dl_d2h_bytes += e.dl_d2h_bytes;
+      for (size_t j = 0; j < of[p].size(); j++) out[of[p][j]] = std::move(r[j]);
+      if (profiling) for (auto& kt : e.dl_times) times.push_back(kt);
     }
   }
 };
@@ -919,6 +952,32 @@ int LM_API(cursor_at)(void* c, const lm_cursor_at_query_c* qs, size_t n, lm_curs
     return 0;
   } catch (const std::exception& e) { x->err = e.what(); return -1; }
 }
+// ---- Text / List deltas from a version to the rendered one (include/loro_merge.h): on the device, from the trackers and op rows of
+// the last lm_run (lm_k_delta.h)
+typedef struct lm_delta_query_c { size_t doc; const uint8_t* from_vv; size_t from_vv_len; } lm_delta_query_c;
+typedef struct lm_delta_result_c { int32_t status; uint32_t other_changed; const uint8_t* json; size_t json_len; } lm_delta_result_c;
+int LM_API(delta)(void* c, const lm_delta_query_c* qs, size_t n, int units, lm_delta_result_c* out) {
+  auto* x = (lm_ctx_impl*)c;
+  try {
+    if (units < 0 || units > 1) throw std::runtime_error("lm_delta: units is 0 (Unicode scalars) or 1 (UTF-16 code units)");
+    std::vector<lm::Engine::DeltaIn> in(n);
+    for (size_t k = 0; k < n; k++) {
+      if (qs[k].doc >= x->api_docs()) throw std::runtime_error("lm_delta: no such document");
+      in[k].doc = (uint32_t)qs[k].doc; in[k].vv = qs[k].from_vv; in[k].vv_len = qs[k].from_vv ? qs[k].from_vv_len : 0;
+    }
+    std::vector<lm::Engine::DeltaOut> r;
+    x->delta(in, units, r);
+    x->dl_json.resize(n);
+    for (size_t k = 0; k < n; k++) {
+      x->dl_json[k].swap(r[k].json);
+      x->dl_json[k].push_back(0);   // (never an empty vector: json is a valid pointer for every query)
+      out[k].status = r[k].status; out[k].other_changed = r[k].other_changed;
+      out[k].json = x->dl_json[k].data(); out[k].json_len = x->dl_json[k].size() - 1;
+    }
+    return 0;
+  } catch (const std::exception& e) { x->err = e.what(); return -1; }
+}
+uint64_t LM_API(delta_bytes)(void* c) { return ((lm_ctx_impl*)c)->dl_d2h_bytes; }
 int LM_API(get_stats)(void* c, lm_run_stats_c* s) {
   auto* x = (lm_ctx_impl*)c;
   s->n_docs = x->api_docs(); s->n_blobs = 0; s->in_bytes = 0; s->out_bytes = 0;

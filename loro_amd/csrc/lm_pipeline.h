@@ -25,6 +25,7 @@
 #include "lm_k_lca.h"
 #include "lm_k_richtext.h"
 #include "lm_k_cursor.h"
+#include "lm_k_delta.h"
 #include "lm_snapshot.h"
 #include "lm_export.h"
 #include "lm_snapshot_base.h"
@@ -131,6 +132,11 @@ struct Engine {
   DBuf b_cur_doc, b_cur_dg, b_cur_grp, b_cur_q, b_cur_names, b_cur_res;
   bool keep_tombstones = false;                   // the next runs replay without the linear prefix (it drops what it deletes from the leaves: cursor_needs_tombstones)
   double cur_ms = 0;                              // k_cursor of the last call (profiling)
+  // lm_delta (lm_k_delta.h)
+  DBuf b_dl_q, b_dl_bnd, b_dl_bits, b_dl_res, b_dl_out, b_dl_off, b_dl_pack, b_dl_poff;
+  uint64_t dl_d2h_bytes = 0;                      // bytes the last lm_delta copied back (result rows + the packed JSON)
+  std::vector<KernelTime> dl_times;               // k_delta_mark / k_delta of the last call (profiling)
+  int dl_launches = 0;                            // k_delta launches of the last lm_delta (2: a slab was too small)
   std::vector<KernelTime> times;
   bool profiling = false;
   std::string last_error;
@@ -305,6 +311,7 @@ struct Engine {
                    &b_cont_root0, &b_cont_nroot, &b_prof, &b_hash, &b_order, &b_ht_key, &b_ht_pfx, &b_ht_best, &b_ht0, &b_ht_cap, &b_ht_list, &b_ht_cnt, &b_slab, &b_vslab, &b_slab_off, &b_vslab_off, &b_slab2, &b_slab2_off, &b_out, &b_out_off,
                    &b_vv_out, &b_vv_off, &b_tk, &b_res, &b_dir_out2, &b_dir_b, &b_dir_b2, &b_doc_saved, &b_elem_cap, &b_old_blobs, &b_prev_doc, &b_prev_uniq, &b_prev_end, &b_lca_out, &b_lca_scratch, &b_lca_off};
     for (DBuf* b : all) b->release();
+    for (DBuf* b : {&b_dl_q, &b_dl_bnd, &b_dl_bits, &b_dl_res, &b_dl_out, &b_dl_off, &b_dl_pack, &b_dl_poff}) b->release();
   }
 
   // ---- stage: pack the blobs (16-byte aligned starts) and upload
@@ -1672,36 +1679,40 @@ struct Engine {
     lmbe::sync();
     // canonical member order: a document that lists several Text containers has its members put into the bytewise order of their
     // JSON-encoded keys (the kernel writes them in container-table order); bytes are moved, never changed
-    std::vector<uint8_t> tmp;
     for (uint32_t i = 0; i < n_docs; i++) {
       if (h_rt_status[i] != ST_OK || h_cnt[i] < 2 || h_rt_len[i] < 2) continue;
-      uint8_t* p = h_rt.data() + h_rt_off[i];
-      const size_t n = h_rt_len[i];
-      std::vector<std::pair<size_t, size_t>> mem;   // [begin, end) of every member inside the outer braces
-      size_t b = 1;
-      int depth = 0;
-      bool in_str = false;
-      for (size_t k = 1; k + 1 < n; k++) {
-        const uint8_t c = p[k];
-        if (in_str) { if (c == '\\') k++; else if (c == '"') in_str = false; continue; }
-        if (c == '"') in_str = true;
-        else if (c == '[' || c == '{') depth++;
-        else if (c == ']' || c == '}') depth--;
-        else if (c == ',' && depth == 0) { mem.emplace_back(b, k); b = k + 1; }
-      }
-      mem.emplace_back(b, n - 1);
-      if (mem.size() != h_cnt[i]) { h_rt_status[i] = ST_INTERNAL; continue; }
-      auto key_end = [&](const std::pair<size_t, size_t>& m) { size_t k = m.first + 1; while (k < m.second && p[k] != '"') k += p[k] == '\\' ? 2 : 1; return k; };
-      std::stable_sort(mem.begin(), mem.end(), [&](const std::pair<size_t, size_t>& x, const std::pair<size_t, size_t>& y) {
-        const size_t xe = key_end(x), ye = key_end(y), xl = xe - x.first, yl = ye - y.first;
-        const int c = memcmp(p + x.first, p + y.first, xl < yl ? xl : yl);
-        return c != 0 ? c < 0 : xl < yl;
-      });
-      tmp.assign(1, '{');
-      for (size_t m = 0; m < mem.size(); m++) { if (m) tmp.push_back(','); tmp.insert(tmp.end(), p + mem[m].first, p + mem[m].second); }
-      tmp.push_back('}');
-      if (tmp.size() == n) memcpy(p, tmp.data(), n); else h_rt_status[i] = ST_INTERNAL;
+      if (!order_members(h_rt.data() + h_rt_off[i], h_rt_len[i], h_cnt[i])) h_rt_status[i] = ST_INTERNAL;
     }
+  }
+  // the `cnt` members of the JSON object at p[0, n) put into the bytewise order of their JSON-encoded keys (false: the object does not
+  // hold that many members)
+  static bool order_members(uint8_t* p, size_t n, uint32_t cnt) {
+    std::vector<std::pair<size_t, size_t>> mem;   // [begin, end) of every member inside the outer braces
+    size_t b = 1;
+    int depth = 0;
+    bool in_str = false;
+    for (size_t k = 1; k + 1 < n; k++) {
+      const uint8_t c = p[k];
+      if (in_str) { if (c == '\\') k++; else if (c == '"') in_str = false; continue; }
+      if (c == '"') in_str = true;
+      else if (c == '[' || c == '{') depth++;
+      else if (c == ']' || c == '}') depth--;
+      else if (c == ',' && depth == 0) { mem.emplace_back(b, k); b = k + 1; }
+    }
+    mem.emplace_back(b, n - 1);
+    if (mem.size() != cnt) return false;
+    auto key_end = [&](const std::pair<size_t, size_t>& m) { size_t k = m.first + 1; while (k < m.second && p[k] != '"') k += p[k] == '\\' ? 2 : 1; return k; };
+    std::stable_sort(mem.begin(), mem.end(), [&](const std::pair<size_t, size_t>& x, const std::pair<size_t, size_t>& y) {
+      const size_t xe = key_end(x), ye = key_end(y), xl = xe - x.first, yl = ye - y.first;
+      const int c = memcmp(p + x.first, p + y.first, xl < yl ? xl : yl);
+      return c != 0 ? c < 0 : xl < yl;
+    });
+    std::vector<uint8_t> tmp(1, '{');
+    for (size_t m = 0; m < mem.size(); m++) { if (m) tmp.push_back(','); tmp.insert(tmp.end(), p + mem[m].first, p + mem[m].second); }
+    tmp.push_back('}');
+    if (tmp.size() != n) return false;
+    memcpy(p, tmp.data(), n);
+    return true;
   }
 
   // ---- lm_cursor_pos / lm_cursor_at (lm_k_cursor.h): ids -> positions, positions -> ids, from the trackers the last run left.
@@ -1794,6 +1805,182 @@ struct Engine {
     lmbe::flush_times(t);
     for (auto& kt : t) cur_ms += kt.ms;
     for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
+  }
+
+  // ---- lm_delta (lm_k_delta.h): the Text / List deltas from a version A (the query's from_vv) to the version the last run rendered.
+  // The host parses and validates A, takes V from the version vector the run rendered, hands both to the device as per-peer-index
+  // counters, sizes two bitmaps per query from the document's element slots, and launches k_delta_mark (op rows -> deleted-in-A /
+  // deleted-in-V bits) and k_delta (one wave per query) into optimistic slabs — twice the document's JSON + a few KB; a query that
+  // needs more sends the call's queries through k_delta once more at exact sizes (the bitmaps are kept).  Only what was written
+  // crosses to the host: the result rows (16 bytes per query), then k_delta_pack moves the queries' bytes out of their slabs into one
+  // dense buffer (16-byte aligned pieces at the exclusive scan of the sizes) and that buffer comes back in one copy — dl_d2h_bytes
+  // counts both.  LM_DELTA_SKEW=1 (tests of the self-check only) hands the device a V that is one counter short for every peer:
+  // the status words then disagree with the id sets and every such query must come back LM_UNSUPPORTED.
+  struct DeltaIn { uint32_t doc; const uint8_t* vv; size_t vv_len; };
+  struct DeltaOut { int32_t status = ST_OK; uint32_t other_changed = 0; std::vector<uint8_t> json; };
+  // VersionVector::encode (postcard: n, then peer u64 / counter i32 as LEB128, zigzag): false when the bytes are not one
+  static bool delta_parse_vv(const uint8_t* p, size_t n, std::map<uint64_t, int64_t>& vv) {
+    if (!p || !n) return true;
+    size_t at = 0;
+    auto uleb = [&](uint64_t& v) -> bool {
+      v = 0;
+      for (uint32_t sh = 0; sh < 70; sh += 7) {
+        if (at >= n) return false;
+        const uint8_t x = p[at++];
+        if (sh == 63 && x > 1) return false;
+        v |= (uint64_t)(x & 0x7f) << sh;
+        if (x < 0x80) return true;
+      }
+      return false;
+    };
+    uint64_t cnt, peer, z;
+    if (!uleb(cnt) || cnt > n) return false;
+    for (uint64_t i = 0; i < cnt; i++) {
+      if (!uleb(peer) || !uleb(z) || z > 0xFFFFFFFFull) return false;
+      vv[peer] = (int64_t)(z >> 1) ^ -(int64_t)(z & 1);
+    }
+    return at == n;
+  }
+  void delta(const std::vector<DeltaIn>& in, int units, std::vector<DeltaOut>& out) {
+    lmbe::bind(sc);
+    if (!ran) throw std::runtime_error("lm_delta before lm_run");
+    if (shared_mode != 0) throw std::runtime_error("lm_delta: a folded batch has to be unfolded first");
+    out.assign(in.size(), DeltaOut());
+    dl_times.clear();
+    dl_launches = 0;
+    struct DocInfo { std::vector<uint64_t> peers; std::vector<uint32_t> V; int32_t status = ST_OK; };
+    std::map<uint32_t, DocInfo> info;
+    std::vector<uint32_t> idx, bnd;
+    std::vector<DlQuery> qs;
+    std::vector<uint64_t> off(1, 0);
+    uint64_t words = 0;
+    uint32_t blocks = 0;
+    const bool skew = getenv("LM_DELTA_SKEW") != nullptr;
+    dl_d2h_bytes = 0;
+    std::vector<uint8_t> buf;
+    for (size_t k = 0; k < in.size(); k++) {
+      const uint32_t doc = in[k].doc;
+      if (doc >= n_docs) throw std::runtime_error("lm_delta: no such document");
+      const DocMeta& m = h_doc[doc];
+      DeltaOut& o = out[k];
+      if (m.status != ST_OK) { o.status = m.status; continue; }
+      if (m.flags & DF_FRONT_ERR) { o.status = m.front_err; continue; }
+      std::map<uint64_t, int64_t> A;
+      if (!delta_parse_vv(in[k].vv, in[k].vv_len, A)) { o.status = ST_DECODE_ERROR; continue; }
+      auto it = info.find(doc);
+      if (it == info.end()) {   // the document's peer table and the version the run rendered, once per call
+        DocInfo di;
+        di.peers.resize(m.n_peers);
+        di.V.assign(m.n_peers, 0);
+        if (m.n_peers) lmbe::d2h(di.peers.data(), b_peer_uniq.as<uint64_t>() + m.praw0, (size_t)m.n_peers * 8);
+        buf.resize(m.vv_len);
+        if (m.vv_len) lmbe::d2h(buf.data(), b_vv_out.as<uint8_t>() + h_vv_off[doc], m.vv_len);
+        lmbe::sync();
+        std::map<uint64_t, int64_t> V;
+        if (m.n_peers > MAX_PEERS || !delta_parse_vv(buf.data(), buf.size(), V)) di.status = ST_UNSUPPORTED;
+        for (auto& kv : V) {
+          auto pi = std::lower_bound(di.peers.begin(), di.peers.end(), kv.first);
+          if (kv.second <= 0) continue;
+          if (pi == di.peers.end() || *pi != kv.first) { di.status = ST_UNSUPPORTED; break; }   // (a version the op rows do not span: no rendering from ids)
+          di.V[pi - di.peers.begin()] = (uint32_t)kv.second;
+        }
+        it = info.emplace(doc, std::move(di)).first;
+      }
+      const DocInfo& di = it->second;
+      if (di.status != ST_OK) { o.status = di.status; continue; }
+      std::vector<uint32_t> a(m.n_peers, 0);
+      bool inside = true;
+      for (auto& kv : A) {
+        if (kv.second <= 0) continue;
+        auto pi = std::lower_bound(di.peers.begin(), di.peers.end(), kv.first);
+        if (pi == di.peers.end() || *pi != kv.first || (uint64_t)kv.second > di.V[pi - di.peers.begin()]) { inside = false; break; }
+        a[pi - di.peers.begin()] = (uint32_t)kv.second;
+      }
+      if (!inside) { o.status = ST_FRONTIERS_NOT_FOUND; continue; }
+      if (doc < h_fused.size() && h_fused[doc]) {   // an LWW Map document decoded without op rows: Maps only
+        for (uint32_t p = 0; p < m.n_peers; p++) if (di.V[p] > a[p]) o.other_changed = 1u;
+        o.json = {'{', '}'};
+        continue;
+      }
+      DlQuery q;
+      memset(&q, 0, sizeof q);
+      q.doc = doc; q.n_bnd = m.n_peers; q.bnd0 = bnd.size();
+      bnd.insert(bnd.end(), a.begin(), a.end());
+      bnd.insert(bnd.end(), di.V.begin(), di.V.end());
+      if (skew) for (uint32_t p = 0; p < m.n_peers; p++) if (bnd[bnd.size() - m.n_peers + p] > a[p]) bnd[bnd.size() - m.n_peers + p]--;
+      q.n_bits = m.atoms;
+      if (resident && doc < tk_elem_cap.size() && tk_elem_cap[doc] > q.n_bits) q.n_bits = tk_elem_cap[doc];
+      q.n_words = q.n_bits / 32 + 1;
+      q.bits0 = words;
+      words += 2ull * q.n_words;
+      q.row_blk0 = blocks;
+      blocks += cdiv(m.n_op, 64);
+      const uint64_t cap = 2ull * m.out_len + 64ull * m.n_cont + 1024;
+      off.push_back(off.back() + ((cap + 15) & ~15ull));
+      qs.push_back(q);
+      idx.push_back((uint32_t)k);
+    }
+    if (qs.empty()) return;
+    const size_t nq = qs.size();
+    bnd.push_back(0);
+    b_dl_q.ensure(nq * sizeof(DlQuery)); b_dl_bnd.ensure(bnd.size() * 4); b_dl_bits.ensure((words + 1) * 4); b_dl_res.ensure(nq * sizeof(DlRes));
+    lmbe::h2d(b_dl_q.p, qs.data(), nq * sizeof(DlQuery));
+    lmbe::h2d(b_dl_bnd.p, bnd.data(), bnd.size() * 4);
+    lmbe::dmemset(b_dl_bits.p, 0, (words + 1) * 4);
+    lmbe::dmemset(b_dl_res.p, 0, nq * sizeof(DlRes));
+    Dev d = last_d;
+    std::vector<DlRes> r(nq);
+    lmbe::reset_times();
+    if (blocks) {
+      lmbe::tic(profiling);
+      LM_LAUNCH(k_delta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (uint32_t)nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_res.as<DlRes>());
+      lmbe::toc("k_delta_mark", dl_times, profiling);
+    }
+    auto pass = [&]() {
+      b_dl_out.ensure(off[nq] + 64);
+      b_dl_off.ensure((nq + 1) * 8);
+      lmbe::h2d(b_dl_off.p, off.data(), (nq + 1) * 8);
+      lmbe::tic(profiling);
+      LM_LAUNCH(k_delta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), (const uint32_t*)b_dl_bits.as<uint32_t>(), b_dl_out.as<uint8_t>(),
+                (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>(), units);
+      lmbe::toc("k_delta", dl_times, profiling);
+      dl_launches++;
+      lmbe::d2h(r.data(), b_dl_res.p, nq * sizeof(DlRes));
+      lmbe::sync();
+    };
+    auto over = [&](size_t j) { return r[j].status == ST_OK && r[j].len > off[j + 1] - off[j]; };
+    pass();
+    bool any_over = false;
+    for (size_t j = 0; j < nq; j++) any_over |= over(j);
+    if (any_over) {   // a slab was too small: every query once more at exact sizes
+      for (size_t j = 0; j < nq; j++) off[j + 1] = off[j] + (r[j].status == ST_OK ? ((uint64_t)r[j].len + 15) & ~15ull : 0);
+      pass();
+      for (size_t j = 0; j < nq; j++) if (over(j)) r[j].status = ST_INTERNAL;
+    }
+    // only the bytes that were written come back: packed on the device, one copy
+    std::vector<uint64_t> poff(nq + 1, 0);
+    for (size_t j = 0; j < nq; j++) poff[j + 1] = poff[j] + (r[j].status == ST_OK ? ((uint64_t)r[j].len + 15) & ~15ull : 0);
+    buf.resize(poff[nq] + 1);
+    if (poff[nq]) {
+      b_dl_pack.ensure(poff[nq] + 64);
+      b_dl_poff.ensure((nq + 1) * 8);
+      lmbe::h2d(b_dl_poff.p, poff.data(), (nq + 1) * 8);
+      lmbe::tic(profiling);
+      LM_LAUNCH(k_delta_pack, nq, 64, (const uint8_t*)b_dl_out.as<uint8_t>(), (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_pack.as<uint8_t>(), (const uint64_t*)b_dl_poff.as<uint64_t>());
+      lmbe::toc("k_delta_pack", dl_times, profiling);
+      lmbe::d2h(buf.data(), b_dl_pack.p, poff[nq]);
+    }
+    lmbe::sync();
+    lmbe::flush_times(dl_times);
+    dl_d2h_bytes = poff[nq] + (uint64_t)dl_launches * nq * sizeof(DlRes);
+    for (size_t j = 0; j < nq; j++) {
+      DeltaOut& o = out[idx[j]];
+      o.status = r[j].status;
+      if (r[j].status != ST_OK) continue;
+      o.other_changed = r[j].other_changed ? 1u : 0u;
+      o.json.assign(buf.begin() + poff[j], buf.begin() + poff[j] + r[j].len);
+      if (r[j].cnt >= 2 && !order_members(o.json.data(), o.json.size(), r[j].cnt)) { o.status = ST_INTERNAL; o.json.clear(); }
+    }
   }
 
   // ---- lm_export: the updates document `i` holds beyond `from_vv` (lm_export.h).  The blobs come back from the arena, the
