@@ -1104,7 +1104,7 @@ struct Engine {
       }
       m.vvh0_lo = (uint32_t)vvh; m.vvh0_hi = (uint32_t)(vvh >> 32);
       if (ok) { elem += ((uint64_t)m.atoms + 15) & ~15ull; leaves += lc; vvh += (uint64_t)m.n_nodes * m.n_peers; }   // element slices start at multiples of 16 slots (k_integrate_span clears loc[] four entries per store; tb[] slices start 16-byte aligned)
-      if (lc > dir_cap) dir_cap = lc;
+      if (ok && m.leaf_cap > dir_cap) dir_cap = m.leaf_cap;   // (a resident document's pool has room to grow beyond lc: the worst-case directory covers the pool, or the retry launch would refuse the document)
       // optimistic LDS directory: leaves are ≈3/4 full in practice (≈48 elements); sized for 40 per leaf
       uint32_t lo = ok ? m.n_elems / 40 + 2 * m.n_cont + 16 : 0;
       if (ok && span) { uint32_t los = (uint32_t)((3ull * m.n_op / 2) / 40) + 2 * m.n_cont + 16; if (los < lo) lo = los; }

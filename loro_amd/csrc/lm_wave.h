@@ -79,8 +79,45 @@ typedef const uint8_t* lm_lds_bytes;
 
 namespace lmw {
 static constexpr int WAVE = 64;
+// Switching fibers is most of what the harness does.  On x86-64 the switch is done here: the callee-saved registers and the two
+// floating-point control words, and nothing else — glibc's swapcontext also sets the signal mask, one system call per switch, which
+// the fibers have no use for.  Elsewhere: ucontext.
+#if defined(__x86_64__) && defined(__GNUC__) && !defined(LM_EMU_UCONTEXT)
+struct EmuCtx { void* sp = nullptr; };
+// saves the caller on its own stack, leaves its stack pointer in *from, continues on stack pointer `to`
+__attribute__((naked, noinline)) static void emu_switch_sp(void** /*from: rdi*/, void* /*to: rsi*/) {
+  __asm__ volatile(
+      "pushq %rbp\n\tpushq %rbx\n\tpushq %r12\n\tpushq %r13\n\tpushq %r14\n\tpushq %r15\n\t"
+      "subq $8, %rsp\n\tstmxcsr (%rsp)\n\tfnstcw 4(%rsp)\n\t"
+      "movq %rsp, (%rdi)\n\tmovq %rsi, %rsp\n\t"
+      "ldmxcsr (%rsp)\n\tfldcw 4(%rsp)\n\taddq $8, %rsp\n\t"
+      "popq %r15\n\tpopq %r14\n\tpopq %r13\n\tpopq %r12\n\tpopq %rbx\n\tpopq %rbp\n\tret\n\t");
+}
+inline void emu_ctx_switch(EmuCtx* from, EmuCtx* to) { emu_switch_sp(&from->sp, to->sp); }
+// a context that enters fn() on the given stack at its first switch; fn never returns (it switches away for good)
+inline void emu_ctx_make(EmuCtx* c, char* stack, size_t size, void (*fn)()) {
+  uint64_t* top = (uint64_t*)(((uintptr_t)stack + size) & ~(uintptr_t)15);
+  top[-1] = 0;                       // where fn's return address would be: fn starts with rsp = 8 mod 16, as after a call
+  top[-2] = (uint64_t)(uintptr_t)fn; // popped by the switch's ret
+  for (int i = 3; i <= 8; i++) top[-i] = 0;   // rbp rbx r12 r13 r14 r15
+  uint32_t* fp = (uint32_t*)(top - 9);
+  fp[0] = 0x1F80;                    // MXCSR and x87 control word as a new thread has them
+  fp[1] = 0x037F;
+  c->sp = top - 9;
+}
+#else
+struct EmuCtx { ucontext_t uc; };
+inline void emu_ctx_switch(EmuCtx* from, EmuCtx* to) { swapcontext(&from->uc, &to->uc); }
+inline void emu_ctx_make(EmuCtx* c, char* stack, size_t size, void (*fn)()) {
+  getcontext(&c->uc);
+  c->uc.uc_stack.ss_sp = stack;
+  c->uc.uc_stack.ss_size = size;
+  c->uc.uc_link = nullptr;
+  makecontext(&c->uc, fn, 0);
+}
+#endif
 struct EmuFiber {
-  ucontext_t ctx;
+  EmuCtx ctx;
   char* stack = nullptr;
   bool done = false;
   int tid = 0;
@@ -94,7 +131,7 @@ struct EmuWave {
 struct EmuBlock {
   std::vector<EmuFiber> fibers;
   std::vector<EmuWave> waves;
-  ucontext_t sched;
+  EmuCtx sched;
   int cur = 0, bid = 0, bdim = 0;
   int blk_arrived = 0, blk_live = 0;
   uint64_t blk_gen = 0;
@@ -111,7 +148,7 @@ inline EmuBlock*& emu_cur() {
 }
 inline void emu_yield() {
   EmuBlock* b = emu_cur();
-  swapcontext(&b->fibers[b->cur].ctx, &b->sched);
+  emu_ctx_switch(&b->fibers[b->cur].ctx, &b->sched);
 }
 inline void emu_trampoline() {
   EmuBlock* b = emu_cur();
@@ -124,11 +161,12 @@ inline void emu_trampoline() {
   b->progress++;
   if (w.live > 0 && w.arrived == w.live) { w.arrived = 0; w.gen++; }
   if (b->blk_live > 0 && b->blk_arrived == b->blk_live) { b->blk_arrived = 0; b->blk_gen++; }
-  swapcontext(&f.ctx, &b->sched);
+  emu_ctx_switch(&f.ctx, &b->sched);
 }
 // run one workgroup of `bdim` threads
 inline void emu_run_block(int bid, int bdim, std::function<void()> body) {
   static const size_t STACK = 256 * 1024;
+  static thread_local std::vector<char*> pool;   // the fibers' stacks, kept from workgroup to workgroup (an allocation of this size is a mapping of its own each time)
   EmuBlock blk;
   blk.bid = bid;
   blk.bdim = bdim;
@@ -141,12 +179,12 @@ inline void emu_run_block(int bid, int bdim, std::function<void()> body) {
   for (int t = 0; t < bdim; t++) {
     EmuFiber& f = blk.fibers[t];
     f.tid = t;
-    f.stack = (char*)malloc(STACK);
-    getcontext(&f.ctx);
-    f.ctx.uc_stack.ss_sp = f.stack;
-    f.ctx.uc_stack.ss_size = STACK;
-    f.ctx.uc_link = nullptr;
-    makecontext(&f.ctx, (void (*)())emu_trampoline, 0);
+    if (prev) f.stack = (char*)malloc(STACK);   // (a workgroup run from inside a fiber: that fiber's stack is in use)
+    else {
+      if ((int)pool.size() <= t) pool.push_back((char*)malloc(STACK));
+      f.stack = pool[t];
+    }
+    emu_ctx_make(&f.ctx, f.stack, STACK, emu_trampoline);
     blk.waves[t >> 6].live++;
   }
   int remaining = bdim;
@@ -161,11 +199,11 @@ inline void emu_run_block(int bid, int bdim, std::function<void()> body) {
     for (int t = 0; t < bdim; t++) {
       if (blk.fibers[t].done) continue;
       blk.cur = t;
-      swapcontext(&blk.sched, &blk.fibers[t].ctx);
+      emu_ctx_switch(&blk.sched, &blk.fibers[t].ctx);
       if (!blk.fibers[t].done) remaining++;
     }
   }
-  for (auto& f : blk.fibers) free(f.stack);
+  if (prev) for (auto& f : blk.fibers) free(f.stack);
   emu_cur() = prev;
 }
 inline std::vector<uint64_t>& emu_dyn_buf() { static std::vector<uint64_t> v; return v; }

@@ -70,12 +70,17 @@ def utf16(s, pos):
 class Expect:
     """the oracle's view of one root sequence container of a document at one version"""
 
-    def __init__(self, all_blobs, at_blobs, name, kind, frontiers=None):
-        self.order = sequence_ids(all_blobs, name, kind)
+    def __init__(self, all_blobs, at_blobs, name, kind, frontiers=None, model=None):
+        """model: a _merge_ref.Model of all_blobs' changes — the sequence order and the visible ids are taken from it, not from the oracle
+        (at_blobs must then be all_blobs)"""
+        self.order = sequence_ids(all_blobs, name, kind) if model is None else model.sequence_ids(wire.root_cid(name, kind))
         st, js, vv, _ = _oracle.merge(at_blobs, frontiers)
         assert st == 0
         self.vv = decode_vv(vv)
-        if frontiers is None:
+        if model is not None:
+            assert frontiers is None and at_blobs is all_blobs
+            self.visible = model.visible_ids(wire.root_cid(name, kind))
+        elif frontiers is None:
             self.visible = _oracle.visible_ids(at_blobs, name, kind)
         else:   # (single-writer histories only: the version is a prefix of the blobs)
             raise NotImplementedError
@@ -149,15 +154,23 @@ def fuzz_session(seed, **kw):
     return _fuzz.random_session(seed, n_peers=kw.pop("n_peers", 3), n_steps=kw.pop("n_steps", 80), kinds=("text", "list"), **kw)
 
 
-def fuzz_corpus(seeds, **kw):
-    """(docs, pos queries, expected, at queries, expected) over unstyled Text + List sessions"""
+def fuzz_corpus(seeds, model=False, **kw):
+    """(docs, pos queries, expected, at queries, expected) over unstyled Text + List sessions; model: the writers' views, the sequence
+    order and the visible ids come from the plain merge model (_merge_ref.py) instead of the oracle"""
     docs, pq, pw, aq, aw = [], [], [], [], []
     for seed in seeds:
-        blobs = _fuzz.blobs_of(fuzz_session(seed, **kw))
+        m = None
+        if model:
+            import _merge_ref, _richtext_ref
+            reps = fuzz_session(seed, view=_merge_ref.view, **dict(kw))
+            m = _merge_ref.Model(_richtext_ref.changes_of(reps))
+        else:
+            reps = fuzz_session(seed, **dict(kw))
+        blobs = _fuzz.blobs_of(reps)
         d = len(docs)
         docs.append(blobs)
         rng = random.Random(seed)
-        et, el = Expect(blobs, blobs, "text", wire.KIND_TEXT), Expect(blobs, blobs, "list", wire.KIND_LIST)
+        et, el = Expect(blobs, blobs, "text", wire.KIND_TEXT, model=m), Expect(blobs, blobs, "list", wire.KIND_LIST, model=m)
         for cid, ex, other in ((TEXT, et, el.order), (LIST, el, et.order)):
             (q, w), (q2, w2) = container_queries(d, cid, ex, rng, other)
             pq += q; pw += w; aq += q2; aw += w2

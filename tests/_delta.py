@@ -119,8 +119,9 @@ def _width(ch, units):
 class At:
     """the oracle's view of the root containers of a document at one version"""
 
-    def __init__(self, blobs):
-        """blobs = updates that hold exactly the version's causal history ([] = the empty version)"""
+    def __init__(self, blobs, ids=None):
+        """blobs = updates that hold exactly the version's causal history ([] = the empty version); ids = {root name: visible ids}
+        from another source than the oracle (the plain merge model, _merge_ref.py)"""
         self.blobs = list(blobs)
         if blobs:
             st, js, vv, _ = _oracle.merge(blobs)
@@ -128,7 +129,7 @@ class At:
         else:
             js, vv = b"{}", None
         self.vv, self.raw, self.value = vv, raw_members(js), json.loads(js)
-        self.ids = {name: (_oracle.visible_ids(blobs, name, kind) if blobs else []) for name, kind, _ in ROOTS}
+        self.ids = {name: (_oracle.visible_ids(blobs, name, kind) if blobs else []) for name, kind, _ in ROOTS} if ids is None else ids
 
 
 def expected(a, v, units=0):
@@ -194,18 +195,26 @@ def kinds_of(ops):
 
 
 # ---- fuzz: unstyled Text + List sessions, A = every recorded snapshot version plus the empty version, V = latest
-def fuzz_corpus(seeds, n_steps=80):
-    """(docs, [(doc, At(A), At(V))])"""
+def fuzz_corpus(seeds, n_steps=80, model=False):
+    """(docs, [(doc, At(A), At(V))]); model: the writers' views and the ids of every At come from the plain merge model
+    (_merge_ref.py) instead of the oracle"""
     docs, pairs = [], []
     for seed in seeds:
         snaps = []
-        reps = _fuzz.random_session(seed, n_peers=3, n_steps=n_steps, kinds=("text", "list"), snapshots=snaps)
+        if model:
+            import _merge_ref, _richtext_ref
+            reps = _fuzz.random_session(seed, n_peers=3, n_steps=n_steps, kinds=("text", "list"), snapshots=snaps, view=_merge_ref.view)
+            m = _merge_ref.Model(_richtext_ref.changes_of(reps))
+            ids = lambda fr: {name: m.visible_ids(wire.root_cid(name, kind), fr) for name, kind, _ in ROOTS}
+        else:
+            reps = _fuzz.random_session(seed, n_peers=3, n_steps=n_steps, kinds=("text", "list"), snapshots=snaps)
+            ids = lambda fr: None
         blobs = _fuzz.blobs_of(reps)
-        v = At(blobs)
+        v = At(blobs, ids(None))
         docs.append(blobs)
-        pairs.append((len(docs) - 1, At([]), v))
-        for _, upd in snaps:
-            pairs.append((len(docs) - 1, At([upd]), v))
+        pairs.append((len(docs) - 1, At([], ids([])), v))
+        for fr, upd in snaps:
+            pairs.append((len(docs) - 1, At([upd], ids(fr)), v))
     return docs, pairs
 
 

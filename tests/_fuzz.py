@@ -7,9 +7,10 @@ ALPHA = "abcdefghijklmnopqrstuvwxyz ABCDEFGH\n\"\\\t" + "äßλ中😀"
 
 
 def random_session(seed, n_peers=3, n_steps=60, kinds=("text",), sync_prob=0.15, max_ins=6, commit_prob=0.4,
-                   peer_base=None, styles=False, snapshots=None, solo_steps=0, max_del=4, solo_peer=0):
+                   peer_base=None, styles=False, snapshots=None, solo_steps=0, max_del=4, solo_peer=0, view=None):
     """Returns (list of blobs in a random delivery order, replicas).  Replicas edit concurrently and sync
-    pairwise; after a sync the receiver's visible sequences are refreshed from the oracle."""
+    pairwise; after a sync the receiver's visible sequences are refreshed from the oracle — or from `view(replica, cid)`
+    (e.g. _merge_ref.view: a corpus written that way holds no decision of the oracle)."""
     rng = random.Random(seed)
     base = peer_base if peer_base is not None else rng.randrange(1, 1 << 40)
     ids = []
@@ -21,10 +22,10 @@ def random_session(seed, n_peers=3, n_steps=60, kinds=("text",), sync_prob=0.15,
     reps = [wire.Replica(p) for p in ids]
 
     def refresh(r):
-        blob = r.export()
+        blob = r.export() if view is None else None
         for cid in list(r.seq.keys()) + [wire.root_cid("text", wire.KIND_TEXT), wire.root_cid("list", wire.KIND_LIST)]:
             if (cid.kind == wire.KIND_TEXT and "text" in kinds) or (cid.kind == wire.KIND_LIST and "list" in kinds):
-                r.set_visible(cid.name, cid.kind, _oracle.visible_ids([blob], cid.name, cid.kind))
+                r.set_visible(cid.name, cid.kind, _oracle.visible_ids([blob], cid.name, cid.kind) if view is None else view(r, cid))
 
     # solo_steps: the session begins with that many steps of ONE replica (reps[solo_peer]) — a history that is a single chain — which
     # every other replica then imports: the version at the hand-over is a critical version (the linear prefix of the batch replay,
@@ -100,10 +101,11 @@ def blobs_of(reps, rng=None, split=False):
     return out
 
 
-def nested_session(seed, n_peers=3, n_steps=120, sync_prob=0.1, max_depth=4):
+def nested_session(seed, n_peers=3, n_steps=120, sync_prob=0.1, max_depth=4, view=None):
     """Random concurrent session over NESTED containers: root Map "nm" and root List "nl" hold child Map / List / Text
     containers (created with insert_container), which hold further children; peers edit any container whose creating
-    op they have seen, children get overwritten / deleted (unreachable afterwards), some children never receive an op."""
+    op they have seen, children get overwritten / deleted (unreachable afterwards), some children never receive an op.
+    `view(replica, cid)`: where the writers take their view of a sequence from after a sync (default: the oracle)."""
     rng = random.Random(seed)
     base = rng.randrange(1, 1 << 40)
     reps = [wire.Replica(base + 7 * i) for i in range(n_peers)]
@@ -114,10 +116,10 @@ def nested_session(seed, n_peers=3, n_steps=120, sync_prob=0.1, max_depth=4):
         return [c for c in conts if c[1] is None or r.vv.get(c[1][0], 0) > c[1][1] or (c[1][0] == r.peer and c[1][1] < r.next_counter)]
 
     def refresh(r):
-        blob = r.export()
+        blob = r.export() if view is None else None
         for cid, _, _ in usable(r):
             if cid.kind in (K.KIND_TEXT, K.KIND_LIST):
-                r.set_visible(cid, cid.kind, _oracle.visible_ids([blob], cid, cid.kind))
+                r.set_visible(cid, cid.kind, _oracle.visible_ids([blob], cid, cid.kind) if view is None else view(r, cid))
 
     for _ in range(n_steps):
         r = rng.choice(reps)

@@ -1,0 +1,291 @@
+"""A PLAIN model of what a merge computes: where concurrent inserts land, which elements a delete hits, who wins a map key,
+what a checkout shows.  No oracle, kernel, decoder or tracker code: no runs, no leaves, no retreat / forward, no LCA, no cut.
+It is small and slow and meant to be read as the definition.  Input: the writers' Change / Op objects (loro_amd.wire,
+`_richtext_ref.changes_of(reps)`).  Output: the deep value as canonical JSON bytes (`_values.to_json`), the version vector
+(`wire.encode_vv`) and the visible element ids of every Text / List.
+
+Versions.  A version is a SET of op ids (peer, counter).  The version an op is applied on is the closure of its change's deps
+plus the change's own atoms in front of the op (diff_calc.rs:480-481); the closure is computed by recursion over `deps`,
+memoised per change.  Changes are processed by (lamport, peer, counter), a linear extension of the causal order.
+
+Text / List.  One Python list per container holds every element ever inserted, in sequence order; an element knows its id,
+its origin_left, its origin_right and the ids of the delete atoms that hit it.  An element is VISIBLE at a version P iff its id
+is in P and none of its deleters is.  An insert atom at position `pos`, applied on version P (crdt_rope.rs:63-237):
+  - origin_left = the visible element at pos - 1 (None at 0)                                        (crdt_rope.rs:84-108)
+  - origin_right = the first element behind origin_left that is IN P, tombstones included (None if there is none); the
+    elements between the two are all outside P ("future")                                           (crdt_rope.rs:110-146)
+  - the atom is placed among those by the sibling rule, crdt_rope.rs:158-237, restated literally in `_place`.
+  - "parent right" of (left, right) = the position of `right` iff right's own origin_left == left   (crdt_rope.rs:121-140, :197-210)
+  The atoms of one insert op go through the rule one by one: atom k > 0 finds atom k - 1 at pos + k - 1 as its origin_left and
+  the op's origin_right as its own, which is what a split run holds in the reference (fugue_span.rs Sliceable).
+  A style_start is an element at `pos`; its style_end is an element at min(pos + mark_len + 1, visible length)
+  (diff_calc.rs:1105-1132 "need to shift 1 because we insert the start style anchor before this pos").
+
+Deletes are resolved by position: the targets are the |signed_len| elements visible at P from DeleteSpan::start
+(list_op.rs:303-309, wire._del_start); atom i hits target i, of a reversed span (signed_len < 0) target n-1-i
+(DeleteSpanWithId::slice, list_op.rs:251-277).  The writer recorded the ids it meant (op.del_id…): the model asserts them,
+so a wrong view surfaces at the op that used it.
+
+Map.  Per key the entry with the greatest (lamport, peer) wins (delta/map_delta.rs:26-32), lamport = change.lamport +
+op.counter - change.counter; a map_delete competes like a write and removes the key (map_state.rs:438-449).
+
+Child containers.  A child is part of the value where the list element / the winning map entry that created it is visible
+(state.rs:1294-1329 get_deep_value resolves LoroValue::Container through the parent's value); its id is the creating op's id.
+
+Root containers (diff_calc.rs:299 `!diff.is_empty() || bring_back`, state.rs:1352-1391; docs/ of the reference, "container
+states are created lazily"): a document is imported (diff ∅ → latest) and then, for a checkout, taken to the version (diff
+latest → version); a container state, once created, stays.  So a root Text / List is shown iff something is visible in it at
+the latest version or at the checked-out one, a root Map iff the history holds an op for it (a deleted key is still an entry of
+the diff, diff_calc.rs:553-605).
+
+Checkout: the same functions over the closure of the given frontiers.
+
+NOT modelled: MovableList, Tree, Counter, pending changes (a change whose deps are missing), damaged input.
+"""
+from _values import to_json
+from loro_amd import wire
+
+OUTCOMES = ("inserts", "between", "foreign_left_break", "same_right_break", "same_right_pass", "diff_right_less", "diff_right_greater",
+            "diff_right_equal")
+
+
+class Elem:
+    __slots__ = ("id", "origin_left", "origin_right", "deleters", "what")
+
+    def __init__(self, id, origin_left, origin_right, what):
+        self.id, self.origin_left, self.origin_right, self.what = id, origin_left, origin_right, what
+        self.deleters = []
+
+
+def _visible(e, P):
+    return e.id in P and not any(d in P for d in e.deleters)
+
+
+def _index_of(els, id):
+    for i, e in enumerate(els):
+        if e.id == id:
+            return i
+    raise KeyError(id)
+
+
+def _parent_right(els, left, right):
+    """crdt_rope.rs:121-140 / :197-210: the position of `right`, iff right's own origin_left is `left`"""
+    if right is None:
+        return None
+    i = _index_of(els, right)
+    return i if els[i].origin_left == left else None
+
+
+def _cmp_pos(a, b):
+    """crdt_rope.rs:453-466, Some < None"""
+    if a is not None and b is not None:
+        return (a > b) - (a < b)
+    if a is not None:
+        return -1
+    if b is not None:
+        return 1
+    return 0
+
+
+def _place(els, P, pos, id, what, stats):
+    """insert one element at visible position `pos` of version P"""
+    left_at, seen = -1, 0
+    if pos > 0:
+        for i, e in enumerate(els):
+            if _visible(e, P):
+                seen += 1
+                if seen == pos:
+                    left_at = i
+                    break
+        assert left_at >= 0, ("insert position beyond the visible length", id, pos, seen)
+    origin_left = els[left_at].id if left_at >= 0 else None
+    right_at = left_at + 1
+    while right_at < len(els) and els[right_at].id not in P:
+        right_at += 1
+    origin_right = els[right_at].id if right_at < len(els) else None
+    between = range(left_at + 1, right_at)
+    stats["inserts"] += 1
+    insert_at = left_at + 1
+    if len(between):
+        stats["between"] += 1
+        mine = _parent_right(els, origin_left, origin_right)
+        scanning, visited = False, set()
+        for i in between:
+            o = els[i]
+            if o.origin_left != origin_left and (o.origin_left is None or o.origin_left not in visited):
+                stats["foreign_left_break"] += 1
+                break
+            visited.add(o.id)
+            if o.origin_left == origin_left:
+                if o.origin_right == origin_right:
+                    if o.id[0] > id[0]:
+                        stats["same_right_break"] += 1
+                        break
+                    stats["same_right_pass"] += 1
+                    scanning = False
+                else:
+                    c = _cmp_pos(_parent_right(els, origin_left, o.origin_right), mine)
+                    if c < 0:
+                        stats["diff_right_less"] += 1
+                        scanning = True
+                    elif c == 0:
+                        stats["diff_right_equal"] += 1
+                        if o.id[0] > id[0]:
+                            break
+                        scanning = False
+                    else:
+                        stats["diff_right_greater"] += 1
+                        scanning = False
+            if not scanning:
+                insert_at = i + 1
+    els.insert(insert_at, Elem(id, origin_left, origin_right, what))
+
+
+class Model:
+    def __init__(self, changes):
+        self.changes = sorted(changes, key=lambda c: (c.lamport, c.peer, c.counter))
+        self.by_peer = {}
+        for c in self.changes:
+            self.by_peer.setdefault(c.peer, []).append(c)
+        for chs in self.by_peer.values():
+            chs.sort(key=lambda c: c.counter)
+        self._below = {}          # (peer, counter of a change) -> frozenset: the closure of its deps
+        self.seqs = {}            # cid -> [Elem] in sequence order
+        self.maps = {}            # cid -> key -> [(lamport, peer, op id, value or _GONE)]
+        self.stats = {k: 0 for k in OUTCOMES}
+        self.all_ids = frozenset((c.peer, k) for c in self.changes for k in range(c.counter, c.ctr_end))
+        for c in self.changes:
+            self._apply(c)
+
+    # ---- versions
+    def _change_of(self, id):
+        for c in self.by_peer.get(id[0], ()):
+            if c.counter <= id[1] < c.ctr_end:
+                return c
+        raise KeyError(id)
+
+    def below(self, ch):
+        """closure of the deps of `ch` (and of its peer's earlier changes: a peer's ops are a chain)"""
+        key = (ch.peer, ch.counter)
+        if key not in self._below:
+            deps = list(ch.deps) + ([(ch.peer, ch.counter - 1)] if ch.counter > 0 else [])
+            self._below[key] = frozenset().union(*[self.closure_of_id(d) for d in deps])
+        return self._below[key]
+
+    def closure_of_id(self, id):
+        ch = self._change_of(id)
+        return self.below(ch) | {(ch.peer, k) for k in range(ch.counter, id[1] + 1)}
+
+    def version(self, frontiers=None):
+        """the set of ids of a checkout target; None = everything"""
+        if frontiers is None:
+            return self.all_ids
+        return frozenset().union(*[self.closure_of_id(f) for f in frontiers])
+
+    # ---- replay
+    def _apply(self, ch):
+        base = self.below(ch)
+        for op in ch.ops:
+            P = base | {(ch.peer, k) for k in range(ch.counter, op.counter)}
+            lam = ch.lamport + op.counter - ch.counter
+            if op.kind in ("map_set", "map_delete"):
+                self.maps.setdefault(op.cid, {}).setdefault(op.key, []).append(
+                    (lam, ch.peer, (ch.peer, op.counter), op.value if op.kind == "map_set" else _GONE))
+                continue
+            els = self.seqs.setdefault(op.cid, [])
+            if op.kind == "text_insert":
+                for i, c in enumerate(op.text):
+                    _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("char", c), self.stats)
+            elif op.kind == "list_insert":
+                for i, v in enumerate(op.values):
+                    _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("value", v), self.stats)
+            elif op.kind == "style_start":
+                _place(els, P, op.pos, (ch.peer, op.counter), ("start", op), self.stats)
+            elif op.kind == "style_end":
+                start = next(e.what[1] for e in els if e.id == (ch.peer, op.counter - 1))
+                n_visible = sum(1 for e in els if _visible(e, P))
+                _place(els, P, min(start.pos + start.mark_len + 1, n_visible), (ch.peer, op.counter), ("end",), self.stats)
+            elif op.kind == "delete":
+                n = abs(op.signed_len)
+                first = wire._del_start(op)
+                targets = [e for e in els if _visible(e, P)][first:first + n]
+                assert len(targets) == n, ("delete beyond the visible length", (ch.peer, op.counter))
+                assert [e.id for e in targets] == [(op.del_id[0], op.del_id[1] + j) for j in range(n)], \
+                    ("the delete does not hit the ids its writer meant", (ch.peer, op.counter), op.del_id, [e.id for e in targets])
+                for i in range(n):
+                    targets[i if op.signed_len > 0 else n - 1 - i].deleters.append((ch.peer, op.counter + i))
+            else:
+                raise NotImplementedError(op.kind)
+
+    # ---- reading
+    def visible_ids(self, cid, frontiers=None):
+        V = self.version(frontiers)
+        return [e.id for e in self.seqs.get(cid, ()) if _visible(e, V)]
+
+    def sequence_ids(self, cid):
+        """every element ever inserted, in sequence order (an order that does not depend on the version)"""
+        return [e.id for e in self.seqs.get(cid, ())]
+
+    def sequences(self):
+        return list(self.seqs)
+
+    def _value(self, cid, V):
+        if cid.kind == wire.KIND_MAP:
+            out = {}
+            for key, entries in self.maps.get(cid, {}).items():
+                seen = [e for e in entries if e[2] in V]
+                if seen:
+                    lam, peer, id, v = max(seen, key=lambda e: (e[0], e[1]))
+                    if v is not _GONE:
+                        out[key] = self._resolve(v, id, V)
+            return out
+        els = [e for e in self.seqs.get(cid, ()) if _visible(e, V)]
+        if cid.kind == wire.KIND_TEXT:
+            return "".join(e.what[1] for e in els if e.what[0] == "char")
+        assert cid.kind == wire.KIND_LIST, cid
+        return [self._resolve(e.what[1], e.id, V) for e in els]
+
+    def _resolve(self, v, id, V):
+        if isinstance(v, wire.ContainerValue):
+            return self._value(wire.CID(False, v.kind, "", id[0], id[1]), V)
+        return v
+
+    def value(self, frontiers=None):
+        """the deep value: root name -> plain Python value"""
+        V = self.version(frontiers)
+        roots = {}
+        for cid in list(self.seqs) + list(self.maps):
+            if not cid.root:
+                continue
+            if cid.kind != wire.KIND_MAP and not (self.visible_ids(cid) or any(_visible(e, V) for e in self.seqs[cid])):
+                continue
+            assert cid.name not in roots, "two root containers share a name"
+            roots[cid.name] = self._value(cid, V)
+        return roots
+
+    def json(self, frontiers=None):
+        return to_json(self.value(frontiers)).encode("utf-8")
+
+    def vv(self, frontiers=None):
+        out = {}
+        for p, c in self.version(frontiers):
+            out[p] = max(out.get(p, 0), c + 1)
+        return wire.encode_vv(out)
+
+    def result(self, frontiers=None):
+        """(status, json, vv, pending) as merge_batch returns it"""
+        return (0, self.json(frontiers), self.vv(frontiers), 0)
+
+
+_GONE = object()
+
+
+# ---- a writer's view from the model: what `_fuzz.random_session(view=...)` takes instead of the oracle's refresh
+def view(replica, cid):
+    """visible ids of `cid` in everything `replica` holds (committed changes)"""
+    key = tuple(sorted(replica.vv.items()))
+    cached = getattr(replica, "_merge_ref_view", None)
+    if cached is None or cached[0] != key:
+        cached = (key, Model([c for chs in replica.changes.values() for c in chs]))
+        replica._merge_ref_view = cached
+    return cached[1].visible_ids(cid)
