@@ -163,10 +163,11 @@ def nested_session(seed, n_peers=3, n_steps=120, sync_prob=0.1, max_depth=4, vie
     return reps
 
 
-def movable_session(seed, n_peers=3, n_steps=80, sync_prob=0.15, nested=False, snapshots=None, bulk=0):
+def movable_session(seed, n_peers=3, n_steps=80, sync_prob=0.15, nested=False, snapshots=None, bulk=0, view=None):
     """Random concurrent session over a root MovableList "ml" (+ a Map "map", and with `nested` child containers created
     by insert_container / set_container and a child MovableList under the Map).  Peers see the list through the writer's
-    local element view (wire.Replica.mlist_*), refreshed from the oracle's item order after a sync.  `bulk` > 0 starts
+    local element view (wire.Replica.mlist_*), refreshed from the oracle's item order after a sync — or from
+    `view(replica, cid)` (e.g. _merge_ref.view); the random stream does not depend on it.  `bulk` > 0 starts
     with that many elements inserted by the first peer and synced to everyone (multi-leaf lists)."""
     rng = random.Random(seed)
     base = rng.randrange(1, 1 << 40)
@@ -180,10 +181,10 @@ def movable_session(seed, n_peers=3, n_steps=80, sync_prob=0.15, nested=False, s
         return made is None or r.vv.get(made[0], 0) > made[1] or (made[0] == r.peer and made[1] < r.next_counter)
 
     def refresh(r):
-        blob = r.export()
+        blob = r.export() if view is None else None
         for cid, made in lists + kids:
             if known(r, made) and cid.kind in (K.KIND_TEXT, K.KIND_LIST, ML):
-                r.set_visible(cid, cid.kind, _oracle.visible_ids([blob], cid, cid.kind))
+                r.set_visible(cid, cid.kind, _oracle.visible_ids([blob], cid, cid.kind) if view is None else view(r, cid))
 
     if bulk:
         for i in range(0, bulk, 7):

@@ -38,15 +38,36 @@ latest → version); a container state, once created, stays.  So a root Text / L
 the latest version or at the checked-out one, a root Map iff the history holds an op for it (a deleted key is still an entry of
 the diff, diff_calc.rs:553-605).
 
+MovableList (diff_calc.rs:1669-1984, tracker.rs:289-347, state/movable_list_state.rs, handler.rs:3528-4000).  Its sequence holds
+ITEMS; an ELEMENT is named by the IdLp (peer, lamport) of the insert atom that made it.
+  - insert: a list_insert of n values places n items by `_place`; atom i has the item id (peer, counter + i) and makes the element
+    (peer, lamport + i).  (The writer emits one op per value, handler.rs:3552-3585; encoding fuses contiguous ones.)
+  - delete: the by-position rule above over the ITEMS visible at the op's version, whether an element still points at them or not.
+  - move: a list_move with id (peer, c) at version P does two things under ONE id (tracker.rs:307-336): it deletes the item visible at
+    P at position `move_from` (the model asserts that this item belongs to the element the writer named), and it places a new item
+    with the id (peer, c), pointing at the same element, at position `pos` among the items visible after that delete — tombstones,
+    the one just made included, still count as "in P" for the origin_right search.  As (peer, c) is both the deleter and the new
+    item's id, `_place(els, P | {(peer, c)}, pos, …)` says exactly this.
+  - set: a list_set touches no item.
+  - the value at a version V: walk the items visible at V in sequence order; an item is shown iff it is the item of its element's
+    greatest candidate by (lamport, peer id) among the insert and the moves whose id is in V (last_pos, history_cache.rs:754-1003);
+    the element's value is that of its greatest candidate by (lamport, peer id) among the insert and the sets in V (last_value).
+    A container value resolves to the child whose id is the creating op's id: the insert atom's, or the set op's.
+  - a root MovableList is shown at EVERY version, empty or not, once the history holds an op for it (its diff lists every element the
+    history knows, delta/movable_list.rs:32-34, diff_calc.rs:1880-1924) — unlike a root List.
+
 Checkout: the same functions over the closure of the given frontiers.
 
-NOT modelled: MovableList, Tree, Counter, pending changes (a change whose deps are missing), damaged input.
+NOT modelled: Tree, Counter, pending changes (a change whose deps are missing), damaged input, snapshot state sections.
 """
 from _values import to_json
 from loro_amd import wire
 
 OUTCOMES = ("inserts", "between", "foreign_left_break", "same_right_break", "same_right_pass", "diff_right_less", "diff_right_greater",
             "diff_right_equal")
+# what the element rules of a MovableList decided, at the latest version (Model.movable_outcomes)
+MOVABLE_OUTCOMES = ("concurrent_moves", "winner_has_smaller_peer", "move_tie_on_lamport", "loser_item_alive", "winner_deleted_loser_alive",
+                    "concurrent_sets", "set_tie_on_lamport")
 
 
 class Elem:
@@ -57,8 +78,35 @@ class Elem:
         self.deleters = []
 
 
+class Element:
+    """a MovableList element: its candidates (lamport, peer, op id[, value]) for the position and for the value"""
+    __slots__ = ("insert", "moves", "sets")
+
+    def __init__(self, insert):
+        self.insert, self.moves, self.sets = insert, [], []
+
+
+def _greatest(cands):
+    return max(cands, key=lambda c: (c[0], c[1]))
+
+
 def _visible(e, P):
-    return e.id in P and not any(d in P for d in e.deleters)
+    if e.id not in P:
+        return False
+    for d in e.deleters:
+        if d in P:
+            return False
+    return True
+
+
+def _nth_visible(els, P, n):
+    """index in `els` of the element at visible position `n` of version P, -1 if the visible length is not beyond n"""
+    for i, e in enumerate(els):
+        if _visible(e, P):
+            if n == 0:
+                return i
+            n -= 1
+    return -1
 
 
 def _index_of(els, id):
@@ -89,15 +137,10 @@ def _cmp_pos(a, b):
 
 def _place(els, P, pos, id, what, stats):
     """insert one element at visible position `pos` of version P"""
-    left_at, seen = -1, 0
+    left_at = -1
     if pos > 0:
-        for i, e in enumerate(els):
-            if _visible(e, P):
-                seen += 1
-                if seen == pos:
-                    left_at = i
-                    break
-        assert left_at >= 0, ("insert position beyond the visible length", id, pos, seen)
+        left_at = _nth_visible(els, P, pos - 1)
+        assert left_at >= 0, ("insert position beyond the visible length", id, pos)
     origin_left = els[left_at].id if left_at >= 0 else None
     right_at = left_at + 1
     while right_at < len(els) and els[right_at].id not in P:
@@ -152,6 +195,7 @@ class Model:
         self._below = {}          # (peer, counter of a change) -> frozenset: the closure of its deps
         self.seqs = {}            # cid -> [Elem] in sequence order
         self.maps = {}            # cid -> key -> [(lamport, peer, op id, value or _GONE)]
+        self.elems = {}           # MovableList cid -> element (peer, lamport) -> Element
         self.stats = {k: 0 for k in OUTCOMES}
         self.all_ids = frozenset((c.peer, k) for c in self.changes for k in range(c.counter, c.ctr_end))
         for c in self.changes:
@@ -193,7 +237,9 @@ class Model:
                     (lam, ch.peer, (ch.peer, op.counter), op.value if op.kind == "map_set" else _GONE))
                 continue
             els = self.seqs.setdefault(op.cid, [])
-            if op.kind == "text_insert":
+            if op.cid.kind == wire.KIND_MOVABLE and op.kind != "delete":
+                self._apply_movable(ch, op, P, lam, els)
+            elif op.kind == "text_insert":
                 for i, c in enumerate(op.text):
                     _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("char", c), self.stats)
             elif op.kind == "list_insert":
@@ -216,6 +262,57 @@ class Model:
                     targets[i if op.signed_len > 0 else n - 1 - i].deleters.append((ch.peer, op.counter + i))
             else:
                 raise NotImplementedError(op.kind)
+
+    def _apply_movable(self, ch, op, P, lam, els):
+        elems = self.elems.setdefault(op.cid, {})
+        id = (ch.peer, op.counter)
+        if op.kind == "list_insert":
+            for i, v in enumerate(op.values):
+                assert (ch.peer, lam + i) not in elems
+                elems[(ch.peer, lam + i)] = Element((lam + i, ch.peer, (ch.peer, op.counter + i), v))
+                _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("item", (ch.peer, lam + i)), self.stats)
+        elif op.kind == "list_move":
+            at = _nth_visible(els, P, op.move_from)
+            assert at >= 0, ("move from beyond the visible length", id)
+            assert els[at].what == ("item", op.elem), ("the move does not take the element its writer meant", id, op.elem, els[at].what)
+            els[at].deleters.append(id)
+            elems[op.elem].moves.append((lam, ch.peer, id))
+            _place(els, P | {id}, op.pos, id, ("item", op.elem), self.stats)
+        elif op.kind == "list_set":
+            assert elems[op.elem].insert[2] in P, ("a set of an element its writer has not seen", id)
+            elems[op.elem].sets.append((lam, ch.peer, id, op.value))
+        else:
+            raise NotImplementedError(op.kind)
+
+    def movable_outcomes(self):
+        """MOVABLE_OUTCOMES at the latest version: what the element rules had to decide in this history.  Per element —
+        concurrent_moves: the causal closure of its winning move does not hold another of its moves; winner_has_smaller_peer: one
+        of those has the greater peer id (the lamport decided); move_tie_on_lamport: one of those has the winner's lamport (the
+        peer id decided); winner_deleted_loser_alive: the item of its winner is deleted, another item of its is alive;
+        concurrent_sets / set_tie_on_lamport: the same over its sets.  Per item — loser_item_alive: alive, and no element's
+        winner."""
+        tot = dict.fromkeys(MOVABLE_OUTCOMES, 0)
+        for cid, elems in self.elems.items():
+            alive = {e.id: e.what[1] for e in self.seqs[cid] if _visible(e, self.all_ids)}
+            pointed = set()
+            for name, el in elems.items():
+                win = _greatest([el.insert[:3]] + el.moves)
+                pointed.add(win[2])
+                others = [m for m in el.moves if m[2] != win[2] and m[2] not in self.closure_of_id(win[2])]
+                if others:                           # a move the winner had not seen: (lamport, peer id) decided
+                    tot["concurrent_moves"] += 1
+                    tot["winner_has_smaller_peer"] += any(m[1] > win[1] for m in others)
+                    tot["move_tie_on_lamport"] += any(m[0] == win[0] for m in others)
+                if win[2] not in alive and name in alive.values():
+                    tot["winner_deleted_loser_alive"] += 1
+                if el.sets:
+                    win = _greatest(el.sets)
+                    others = [m for m in el.sets if m[2] != win[2] and m[2] not in self.closure_of_id(win[2])]
+                    if others:
+                        tot["concurrent_sets"] += 1
+                        tot["set_tie_on_lamport"] += any(m[0] == win[0] for m in others)
+            tot["loser_item_alive"] += sum(1 for id in alive if id not in pointed)
+        return tot
 
     # ---- reading
     def visible_ids(self, cid, frontiers=None):
@@ -240,6 +337,14 @@ class Model:
                         out[key] = self._resolve(v, id, V)
             return out
         els = [e for e in self.seqs.get(cid, ()) if _visible(e, V)]
+        if cid.kind == wire.KIND_MOVABLE:
+            out = []
+            for e in els:
+                el = self.elems[cid][e.what[1]]
+                if _greatest([el.insert[:3]] + [m for m in el.moves if m[2] in V])[2] == e.id:      # last_pos
+                    lam, peer, id, v = _greatest([el.insert] + [s for s in el.sets if s[2] in V])   # last_value
+                    out.append(self._resolve(v, id, V))
+            return out
         if cid.kind == wire.KIND_TEXT:
             return "".join(e.what[1] for e in els if e.what[0] == "char")
         assert cid.kind == wire.KIND_LIST, cid
@@ -257,7 +362,7 @@ class Model:
         for cid in list(self.seqs) + list(self.maps):
             if not cid.root:
                 continue
-            if cid.kind != wire.KIND_MAP and not (self.visible_ids(cid) or any(_visible(e, V) for e in self.seqs[cid])):
+            if cid.kind not in (wire.KIND_MAP, wire.KIND_MOVABLE) and not (self.visible_ids(cid) or any(_visible(e, V) for e in self.seqs[cid])):
                 continue
             assert cid.name not in roots, "two root containers share a name"
             roots[cid.name] = self._value(cid, V)
@@ -282,7 +387,8 @@ _GONE = object()
 
 # ---- a writer's view from the model: what `_fuzz.random_session(view=...)` takes instead of the oracle's refresh
 def view(replica, cid):
-    """visible ids of `cid` in everything `replica` holds (committed changes)"""
+    """visible ids of `cid` in everything `replica` holds (committed changes); of a MovableList the ids of its alive ITEMS, pointed at
+    or not, in op-index order — what wire.Replica.mlist_* keeps in `seq`"""
     key = tuple(sorted(replica.vv.items()))
     cached = getattr(replica, "_merge_ref_view", None)
     if cached is None or cached[0] != key:
