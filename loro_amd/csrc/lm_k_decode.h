@@ -21,7 +21,7 @@ struct Dev {  // device pointers of one batch (passed by value to every kernel)
   uint32_t n_blobs, n_docs;
   uint32_t span;              // 1: leaves hold runs (lm_k_integrate_span.h, SP_REC dwords per leaf), 0: one element per slot
   const uint32_t* res_old_blobs;   // resident documents: per document the number of blobs earlier runs already held (nullptr otherwise)
-  uint32_t loc_cleared;       // 1: loc[] was set to NONE by a memset in front of the integrate stage (the waves skip their own clear)
+  uint32_t loc_cleared;       // 1: kept[] was set to 0 by a fill in front of the integrate stage (the waves skip their own clear)
   uint32_t* posdel;           // per document 3 * PD_CAP words: the delete rows the span-granular batch kernels applied by position (lm_k_integrate_span.h ts_del_positional); nullptr = a mismatch is LM_DATA_CORRUPTION
   const uint64_t* posdel_off; // per document (n_docs + 1): its slice of `posdel` in pieces; nullptr = PD_CAP pieces each
   uint32_t* pd_row_idx;       // per op row of the batch: the first piece of a row applied by position in its document's list (documents whose slice exceeds PD_CAP: staged on a snapshot's state); nullptr = no such document
@@ -88,6 +88,7 @@ struct Dev {  // device pointers of one batch (passed by value to every kernel)
   // elements
   uint32_t* cp;          // text: unicode scalar (CP_ANCHOR | op row = style anchor) | list: value offset rel. to the doc's first byte
   uint32_t* loc;         // element → leaf
+  uint32_t* kept;        // span-granular kernels: bit (slot & 31) of word (slot >> 5) = loc[slot] holds a kept entry (lm_k_integrate_span.h sp_keep)
   uint32_t* dcnt;        // resident documents: element → delete ops of the version a tracker is being moved to (ts_sweep_version); nullptr otherwise
   uint8_t* tb;           // span-granular leaves: one byte per Text element — the scalar when it is ASCII, TB_WIDE: cp[] holds it, TB_ANCHOR: a style anchor
   // tracker pools

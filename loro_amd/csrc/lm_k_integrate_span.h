@@ -25,6 +25,7 @@ struct SpanItem { uint32_t id, len, ol, orr, st; };
 struct Ts {   // wave-uniform context of one (document, sequence container) replay
   uint32_t* it;                   // HBM leaf records of the document: [leaf * SP_REC + field * 64 + slot]
   uint32_t* loc;                  // doc element → leaf
+  uint32_t* kept;                 // LM_LOC16: one bit per element slot of the document, set where loc[] holds a kept entry (sp_keep)
   const uint32_t* ebase;          // LDS: element base per peer
   const uint32_t* cur;            // LDS: tracker version per peer at the head of the node being replayed
   const uint32_t* end;            // LDS: version being rendered per peer (no element exists at or beyond it)
@@ -133,25 +134,38 @@ static constexpr uint32_t LOC_SHORT = LM_LOC_SHORT;
 #endif
 static constexpr uint32_t LOC_W = LM_LOC_W;   // a power of two <= 64
 // loc[] is kept only for the HEAD of every item and for the elements whose
-// counter is a multiple of LOC_W — everything else stays NONE.  Items are only ever cut or appended to, never joined, so a head
+// counter is a multiple of LOC_W.  Items are only ever cut or appended to, never joined, so a head
 // stays a head; the nearest kept entry at or below an element of an item, inside its LOC_W-aligned counter window, is therefore an
 // element of the same item (ts_loc_find).  A flush writes 1 + len/16 entries per pending item instead of len.
+// WHICH entries are kept is said by kept[], one bit per element slot, and not by the entry's value: what lies in loc[] where the
+// bit is clear is never looked at, so only the bitmap — 1/32 of loc[]'s bytes — is cleared in front of a replay.  Entries are
+// never erased between two clears: a kept entry only changes its value.  Lanes of one flush often hit the same bitmap word
+// (neighbouring items have neighbouring ids): the bit is set with an atomic OR whose result is not used (no round trip); the lookup
+// reads the word where the ORs execute, at L2 (lmw::load_agent).  (A workgroup-scope OR measured the same)
+// Order: no fence stands between this OR and the load of ts_loc_find (sp_flush_loc; wave_sync, which is only a scheduling barrier;
+// load).  The compiler keeps the two in order because the addresses may alias; the hardware does because one wave's vector-memory
+// operations to one address reach L2 in issue order — what the loc[] store and its load have always relied on.  Whoever changes the
+// scope of either operation or moves the flush has to keep that.
+LM_DEV void sp_keep(Ts& t, uint32_t g, uint32_t L) {
+  t.loc[g] = L;
+  (void)lmw::atomic_or(t.kept + (g >> 5), 1u << (g & 31));
+}
 LM_DEV void sp_set_loc_lanes(Ts& t, const SpanRegs& R, bool pend, uint32_t L) {
   if (!t.loc) return;   // loc[] is not kept yet (ts_build_loc): nothing can ask for an element by id while the replay is one chain
   uint32_t len = pend ? R.len : 0u;
   uint32_t c0 = pid_ctr(R.id);
   uint32_t g = pend ? t.ebase[pid_peer(R.id)] + c0 : 0u;
-  if (pend) t.loc[g] = L;
+  if (pend) sp_keep(t, g, L);
   uint32_t k = LOC_W - (c0 & (LOC_W - 1));             // offset of the first multiple of LOC_W beyond the head
   // (most pending items are short: the trips are taken only while some item still has such an element — four masked trips
   // for every call were 4.5 % of the kernel)
-  for (uint32_t i = 0; i < 4 && lmw::any(k < len); i++, k += LOC_W) if (k < len) t.loc[g + k] = L;
+  for (uint32_t i = 0; i < 4 && lmw::any(k < len); i++, k += LOC_W) if (k < len) sp_keep(t, g + k, L);
   uint64_t m = lmw::ballot(k < len);                   // items with more than four such elements
   while (m) {
     int j = lmw::ffs64(m);
     m &= m - 1;
     uint32_t gj = lmw::bcast(g, j), lj = lmw::bcast(len, j), kj = lmw::bcast(k, j);
-    for (uint32_t kk = kj + LOC_W * (uint32_t)lmw::lane(); kk < lj; kk += 64 * LOC_W) t.loc[gj + kk] = L;
+    for (uint32_t kk = kj + LOC_W * (uint32_t)lmw::lane(); kk < lj; kk += 64 * LOC_W) sp_keep(t, gj + kk, L);
   }
 }
 // leaf of element `pid` (wave-uniform), NONE when no kept entry lies at or below it in its window
@@ -159,8 +173,13 @@ LM_DEV uint32_t ts_loc_find(const Ts& t, uint32_t pid) {
   if (!t.loc) return NONE;
   uint32_t ctr = pid_ctr(pid), lo = ctr & ~(LOC_W - 1), eb = t.ebase[pid_peer(pid)];
   uint32_t lane = (uint32_t)lmw::lane();
-  uint32_t v = (lane < LOC_W && lo + lane <= ctr) ? t.loc[eb + lo + lane] : NONE;
-  uint64_t m = lmw::ballot(v != NONE);
+  // the entry and its bit are two independent loads of one round trip; the bit is read where the ORs execute (lmw::load_agent)
+  const bool in = lane < LOC_W && lo + lane <= ctr;
+  const uint32_t g = eb + lo + lane;
+  uint32_t v = in ? t.loc[g] : NONE;
+  uint32_t w = in ? lmw::load_agent(t.kept + (g >> 5)) : 0u;
+  uint64_t m = lmw::ballot(((w >> (g & 31)) & 1u) != 0);
+  lmw::emu_note_lookup(t.kept, eb + lo, LOC_W);
   if (!m) return NONE;
   int top = 63 - __builtin_clzll((unsigned long long)m);
   return lmw::bcast(v, top);
@@ -1454,10 +1473,14 @@ inline bool ts_check(Ts& t, const char* what, uint32_t row) {
         nf |= !(st & ST_FUT);
         for (uint32_t k = 0; k < ln && t.loc; k++) {
 #ifdef LM_LOC16
-          uint32_t expect = (k == 0 || ((id0 + k) & (LOC_W - 1)) == 0) ? L : NONE;   // kept entries only: heads and multiples of LOC_W
-#else
-          uint32_t expect = L;
+          // the bits are exactly the heads and the multiples of LOC_W; loc[] is looked at only where the bit is set
+          const bool want = k == 0 || ((id0 + k) & (LOC_W - 1)) == 0;
+          const uint32_t gk = ts_g(t, id0 + k);
+          const bool bit = ((t.kept[gk >> 5] >> (gk & 31)) & 1u) != 0;
+          if (bit != want) { fprintf(stderr, "CHECK %s row=%u: kept bit of %u:%u is %d, expected %d (leaf %u)\n", what, row, id0 >> 24, (id0 & 0xffffff) + k, (int)bit, (int)want, L); ok = false; break; }
+          if (!bit) continue;
 #endif
+          const uint32_t expect = L;
           if (t.loc[ts_g(t, id0 + k)] != expect) { fprintf(stderr, "CHECK %s row=%u: loc of %u:%u is %u, item lives in leaf %u\n", what, row, id0 >> 24, (id0 & 0xffffff) + k, t.loc[ts_g(t, id0 + k)], L); ok = false; break; }
         }
       }
@@ -1585,14 +1608,23 @@ LM_DEV void integrate_span_body(Dev d, DevDag g, uint32_t dir_cap, uint32_t pmax
   if (status_fatal(m.status) && !retry_pass) return;
   // RES: the element layout is the stored tracker's (k_res_layout) — loc[] is kept, only the slots new to this run are cleared
   const bool keep_loc = RES && !ML && !retry_pass && (m.flags & DF_LAYOUT_SAME) != 0;
+  uint32_t from = 0;   // first element slot to clear
+  if (keep_loc) from = lmw::first((rs.tk + rs.doc[doc].tk_off)[6]);   // (a multiple of 32, as every peer region's base and extent: k_res_layout; the slots from there on were never used — they hold no kept entry)
+#ifdef LM_LOC16
+  // kept[] of the document := 0 (a slice starts at a multiple of 32 element slots, lm_pipeline.h: no other document's bit lies in
+  // these words).  A kept layout is cleared from its first new slot on, which lies on a word boundary.
+  if (RES || !d.loc_cleared || retry_pass) {
+    uint32_t* kw = d.kept + (elem0 >> 5);
+    for (uint32_t i = (from >> 5) + (uint32_t)lane; i < (m.atoms + 31) / 32; i += 64) kw[i] = 0u;
+  }
+  // MovableList documents keep a dense loc[] besides: k_mlist_post and k_emit_any read it by element after this stage
+  if (ML)
+#endif
   {   // loc[] of the document := NONE, four entries per store (the slice is 16-byte aligned and padded to a multiple of four)
     struct alignas(16) U4 { uint32_t x, y, z, w; };
     U4* l4 = (U4*)(d.loc + elem0);
     const U4 none4 = {NONE, NONE, NONE, NONE};
-    uint32_t from4 = 0;
-    if (keep_loc) from4 = lmw::first((rs.tk + rs.doc[doc].tk_off)[6]) / 4;   // (slices are padded to multiples of four: the boundary group is cleared again only if it was never used — it holds no kept entry, see k_res_layout)
-    if (RES || !d.loc_cleared || retry_pass)
-      for (uint32_t i = from4 + (uint32_t)lane; i < (m.atoms + 3) / 4; i += 64) l4[i] = none4;
+    for (uint32_t i = from / 4 + (uint32_t)lane; i < (m.atoms + 3) / 4; i += 64) l4[i] = none4;
   }
   if (retry_pass) {
     for (uint32_t c = (uint32_t)lane; c < m.n_cont; c += 64) {   // sequence containers only: a Map's flag belongs to k_map_lww
@@ -1662,6 +1694,7 @@ LM_DEV void integrate_span_body(Dev d, DevDag g, uint32_t dir_cap, uint32_t pmax
   Ts t;
   t.it = d.it + (uint64_t)m.leaf0 * SP_REC;
   t.loc = d.loc + elem0;
+  t.kept = d.kept + (elem0 >> 5);
   t.ebase = s_ebase; t.cur = s_cur; t.end = s_end; t.da = s_da; t.db = s_db; t.ds = s_ds; t.ds_on = false;
   t.dir_cap = dir_cap; t.leaf_cap = m.leaf_cap; t.n_leaf = 0; t.err = 0; t.beyond = 0;
   t.n_alive = 0;
@@ -2172,7 +2205,7 @@ LM_DEV void integrate_span_body(Dev d, DevDag g, uint32_t dir_cap, uint32_t pmax
     }
     lmw::mem_fence();
     lmw::block_sync();
-    if (lane == 0) { tk[1] = P; tk[2] = m.n_cont; tk[3] = t.n_leaf; tk[4] = m.elem0_lo; tk[5] = m.elem0_hi; tk[6] = (m.atoms + 3) & ~3u; tk[7] = m.pending_lo | m.pending_hi; tk[8] = m.atoms; tk[0] = 1; }
+    if (lane == 0) { tk[1] = P; tk[2] = m.n_cont; tk[3] = t.n_leaf; tk[4] = m.elem0_lo; tk[5] = m.elem0_hi; tk[6] = (m.atoms + 31) & ~31u; tk[7] = m.pending_lo | m.pending_hi; tk[8] = m.atoms; tk[0] = 1; }
   }
   if (lane == 0) d.doc[doc].pad0 = dir_used;
 #ifdef LM_PROF
@@ -2259,7 +2292,7 @@ LM_KERNEL LM_WAVES_PER_SIMD(LM_RES_WAVES) LM_ONE_WAVE_GROUPS void k_integrate_sp
 // Before the payload fill and the integrate stage of a run: the element layout of a resident document.  A batch lays a
 // document's elements out peer after peer (k_dag_a: base = Σ extents of the peers in front); a resident document would then move
 // every later peer's elements whenever an earlier peer grows — and with them loc[], the payload slots and everything else that
-// is indexed by element.  Here every peer owns a region with room to grow (extent × 1.5 + 64), handed out at the end of the
+// is indexed by element.  Here every peer owns a region with room to grow (extent × 1.5 + 64, rounded up to 32 slots), handed out at the end of the
 // document's slice when the peer is first seen; a known peer keeps its base as long as its extent fits its region, whatever
 // index it has now.  Only when a region (or the slice) is outgrown the document is laid out anew — its stored tracker is then
 // not used (DF_LAYOUT_SAME off: k_elem_fill fills everything, the integrate stage rebuilds loc[] — or replays, for what cannot
@@ -2301,7 +2334,7 @@ LM_KERNEL void k_res_layout(Dev d, DevRes rs) {
     uint32_t p = p0 + (uint32_t)lane;
     bool need = p < P && s_base[p] == NONE;
     uint32_t ext = p < P ? d.peer_ext[m.praw0 + p] : 0u;
-    uint32_t cap = need ? ((ext + ext / 2 + 64 + 3) & ~3u) : 0u;
+    uint32_t cap = need ? ((ext + ext / 2 + 64 + 31) & ~31u) : 0u;   // (multiples of 32 slots: a region begins a word of kept[], so does the part of a kept layout that is new to a run)
     uint32_t inc = lmw::scan_incl_add(cap);
     if (need) { s_base[p] = top + inc - cap; s_cap[p] = cap; }
     top += lmw::bcast(inc, 63);
@@ -2313,7 +2346,7 @@ LM_KERNEL void k_res_layout(Dev d, DevRes rs) {
       for (uint32_t p0 = 0; p0 < P; p0 += 64) {
         uint32_t p = p0 + (uint32_t)lane;
         uint32_t ext = p < P ? d.peer_ext[m.praw0 + p] : 0u;
-        uint32_t cap = p < P ? ((ext + ext / 2 + 64 + 3) & ~3u) : 0u;
+        uint32_t cap = p < P ? ((ext + ext / 2 + 64 + 31) & ~31u) : 0u;
         uint32_t inc = lmw::scan_incl_add(cap);
         if (p < P) { s_base[p] = top + inc - cap; s_cap[p] = cap; }
         top += lmw::bcast(inc, 63);

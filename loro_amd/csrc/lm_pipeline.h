@@ -104,7 +104,7 @@ struct Engine {
   DBuf b_doc, b_peer_uniq, b_peer_end, b_peer_ext, b_peer_base, b_peer_end_all, b_elem_base, b_peer_chg0, b_peer_chg1, b_cont;
   DBuf b_chg_mask, b_chg_sorted, b_chg_lamport, b_chg_skip, b_chg_flag, b_node_first, b_node_last, b_node_order, b_vvh;
   DBuf b_blk_sorted, b_chg_node, b_node_done, b_node_lam;
-  DBuf b_cp, b_loc, b_tb, b_fuse, b_dcnt, b_posdel;
+  DBuf b_cp, b_loc, b_kept, b_tb, b_fuse, b_dcnt, b_posdel;
   DBuf b_it, b_dir_out, b_lf_chunk;
   DBuf b_cont_root0, b_cont_nroot;
   DBuf b_ht_key, b_ht_pfx, b_ht_best, b_ht0, b_ht_cap, b_ht_list, b_ht_cnt;
@@ -189,7 +189,7 @@ struct Engine {
   } sv;
 
   // environment knobs (A/B measurements and tests): read once per staged batch / import, not inside the run
-  struct Knobs { bool span = true, decode_wave = true, no_opt_dir = false, loc_memset = true; int plain = 2; uint32_t dec_slot = 1264, dec_slot_big = 4096, dec_big_mode = 1, dir_opt_max = 0; size_t lds_pad = 0; long long slab_cap = -1; uint32_t ht_opt = 2048, cut_min_rows = 2048, vs_row_cost = 300; bool lww_lds = true, fuse_rows = true, version_sweep = true, span_auto = true, linear = true, posdel = true, reclass = true, redo = true, map_fused = true, snapshot_state = true, snapshot_state_force = false, stage_direct = true; uint32_t mf_min_rows = 2048, mf_chg_ratio = 4, pd_state_pieces = 2; } kn;
+  struct Knobs { bool span = true, decode_wave = true, no_opt_dir = false, loc_memset = true, loc_poison = false; int plain = 2; uint32_t dec_slot = 1264, dec_slot_big = 4096, dec_big_mode = 1, dir_opt_max = 0; size_t lds_pad = 0; long long slab_cap = -1; uint32_t ht_opt = 2048, cut_min_rows = 2048, vs_row_cost = 300; bool lww_lds = true, fuse_rows = true, version_sweep = true, span_auto = true, linear = true, posdel = true, reclass = true, redo = true, map_fused = true, snapshot_state = true, snapshot_state_force = false, stage_direct = true; uint32_t mf_min_rows = 2048, mf_chg_ratio = 4, pd_state_pieces = 2; } kn;
   void read_knobs() {
     Knobs k;
     if (const char* e = getenv("LM_SPAN")) k.span = atoi(e) != 0;
@@ -202,6 +202,7 @@ struct Engine {
     if (const char* e = getenv("LM_LDS_PAD")) k.lds_pad = (size_t)atoi(e);                       // occupancy experiments only
     k.no_opt_dir = getenv("LM_NO_OPT_DIR") != nullptr;
     if (const char* e = getenv("LM_LOC_MEMSET")) k.loc_memset = atoi(e) != 0;
+    if (const char* e = getenv("LM_LOC_POISON")) k.loc_poison = atoi(e) != 0;                       // tests: loc[] := 0 (a valid leaf of every document) in front of the integrate stage — no result may depend on an entry whose kept[] bit is clear
     if (const char* e = getenv("LM_DIR_OPT_MAX")) k.dir_opt_max = (uint32_t)atoi(e);             // tests: force the retry launch
     if (const char* e = getenv("LM_SLAB_CAP")) k.slab_cap = atoll(e);                            // tests: force the re-emit pass
     if (const char* e = getenv("LM_HT_OPT")) k.ht_opt = (uint32_t)atoi(e);                       // slots of a document's optimistic LWW table (a power of two; 0: sized for its Map rows at once; tests: 64 forces the second pass)
@@ -306,7 +307,7 @@ struct Engine {
                    &b_vvo, &b_vvo_off, &b_blk, &b_bcnt, &b_boff, &b_blk_kind, &b_doc_fused, &b_mf_docs, &b_mf_key0, &b_chg, &b_dep_peer, &b_dep_ctr, &b_dep_ci, &b_op, &b_op_val, &b_op_blk, &b_key_off, &b_key_len,
                    &b_cid_raw, &b_cid_map, &b_peer_raw, &b_peer_map, &b_doc, &b_peer_uniq, &b_peer_end, &b_peer_ext, &b_peer_base, &b_peer_end_all, &b_elem_base,
                    &b_peer_chg0, &b_peer_chg1, &b_cont, &b_chg_mask, &b_chg_sorted, &b_chg_lamport, &b_chg_skip, &b_chg_flag, &b_node_first,
-                   &b_node_last, &b_node_order, &b_vvh, &b_blk_sorted, &b_chg_node, &b_node_done, &b_node_lam, &b_cp, &b_loc, &b_tb, &b_it,
+                   &b_node_last, &b_node_order, &b_vvh, &b_blk_sorted, &b_chg_node, &b_node_done, &b_node_lam, &b_cp, &b_loc, &b_kept, &b_tb, &b_it,
                    &b_dir_out, &b_lf_chunk, &b_fuse, &b_dcnt, &b_posdel, &b_pd_off, &b_pd_row,
                    &b_cont_root0, &b_cont_nroot, &b_prof, &b_hash, &b_order, &b_ht_key, &b_ht_pfx, &b_ht_best, &b_ht0, &b_ht_cap, &b_ht_list, &b_ht_cnt, &b_slab, &b_vslab, &b_slab_off, &b_vslab_off, &b_slab2, &b_slab2_off, &b_out, &b_out_off,
                    &b_vv_out, &b_vv_off, &b_tk, &b_res, &b_dir_out2, &b_dir_b, &b_dir_b2, &b_doc_saved, &b_elem_cap, &b_old_blobs, &b_prev_doc, &b_prev_uniq, &b_prev_end, &b_lca_out, &b_lca_scratch, &b_lca_off};
@@ -1071,10 +1072,10 @@ struct Engine {
       if (resident) {
         // the document's slice of the element arena stays where it is while it is large enough (loc[] and the payload slots of
         // earlier runs stay valid, k_res_layout); a larger one is handed out with room to grow
-        // (k_res_layout gives every peer a region of extent x 1.5 + 64 slots: a fresh layout needs at most 1.5 x atoms + 68 per peer)
-        uint64_t need = (uint64_t)m.atoms + m.atoms / 2 + 68ull * (m.n_peers + 1) + 8;
+        // (k_res_layout gives every peer a region of extent x 1.5 + 64 slots, rounded up to 32: a fresh layout needs at most 1.5 x atoms + 96 per peer)
+        uint64_t need = (uint64_t)m.atoms + m.atoms / 2 + 96ull * (m.n_peers + 1) + 8;
         if (ok && need > tk_elem_cap[i]) {
-          uint64_t cap = ((need + need / 2 + 80ull * 8) + 15) & ~15ull;   // (slices start at multiples of 16 element slots)
+          uint64_t cap = ((need + need / 2 + 80ull * 8) + 31) & ~31ull;   // (slices start at multiples of 32 element slots: see the batch slices below)
           if (cap > 0xfffffff0ull) throw std::runtime_error("resident element slice beyond 32-bit indices");
           tk_elem0[i] = elem_top; tk_elem_cap[i] = (uint32_t)cap; elem_top += cap;
         }
@@ -1103,7 +1104,10 @@ struct Engine {
         if (ok && (tk_pcap[i] == 0 || m.n_peers > tk_pcap[i] || m.n_cont > tk_ccap[i])) tk_grow(i, m.n_peers, m.n_cont);   // (a record for every document that runs, an empty one included)
       }
       m.vvh0_lo = (uint32_t)vvh; m.vvh0_hi = (uint32_t)(vvh >> 32);
-      if (ok) { elem += ((uint64_t)m.atoms + 15) & ~15ull; leaves += lc; vvh += (uint64_t)m.n_nodes * m.n_peers; }   // element slices start at multiples of 16 slots (k_integrate_span clears loc[] four entries per store; tb[] slices start 16-byte aligned)
+      // element slices start at multiples of 32 slots.  The rule: NO TWO DOCUMENTS SHARE A WORD OF kept[] (bit = slot & 31 of word slot >> 5) —
+      // different waves clear different documents' words with plain stores, one word per store.  (It also gives what the dense arrays
+      // need: a MovableList document's loc[] is cleared four entries per store, tb[] slices start 16-byte aligned.)
+      if (ok) { elem += ((uint64_t)m.atoms + 31) & ~31ull; leaves += lc; vvh += (uint64_t)m.n_nodes * m.n_peers; }
       if (ok && m.leaf_cap > dir_cap) dir_cap = m.leaf_cap;   // (a resident document's pool has room to grow beyond lc: the worst-case directory covers the pool, or the retry launch would refuse the document)
       // optimistic LDS directory: leaves are ≈3/4 full in practice (≈48 elements); sized for 40 per leaf
       uint32_t lo = ok ? m.n_elems / 40 + 2 * m.n_cont + 16 : 0;
@@ -1138,11 +1142,11 @@ struct Engine {
     if (resident) {
       // arenas that outlive the run: element payloads (a MovableList move keeps the id of the item it deleted in its own slot),
       // the leaf pool and the two generations of the leaf directories
-      b_cp.ensure_keep((elem_top + 1) * 4, b_cp.cap); b_loc.ensure_keep((elem_top + 4) * 4, b_loc.cap); b_dcnt.ensure((elem_top + 1) * 4); b_tb.ensure_keep(elem_top + 16, b_tb.cap);
+      b_cp.ensure_keep((elem_top + 1) * 4, b_cp.cap); b_loc.ensure_keep((elem_top + 4) * 4, b_loc.cap); b_kept.ensure_keep((elem_top / 32 + 4) * 4, b_kept.cap); b_dcnt.ensure((elem_top + 1) * 4); b_tb.ensure_keep(elem_top + 16, b_tb.cap);
       b_it.ensure_keep(((size_t)leaf_top + 1) * SP_REC * 4, b_it.cap);
       for (DBuf* b : {&b_dir_out, &b_dir_out2, &b_dir_b, &b_dir_b2}) b->ensure_keep(((size_t)leaf_top + 1) * 4, b->cap);
     } else {
-      b_cp.ensure((elem + 1) * 4); b_loc.ensure((elem + 4) * 4); b_tb.ensure(elem + 16);
+      b_cp.ensure((elem + 1) * 4); b_loc.ensure((elem + 4) * 4); b_kept.ensure((elem / 32 + 4) * 4); b_tb.ensure(elem + 16);
       if (LM_BATCH_VSWEEP && want_dcnt && span && kn.version_sweep) b_dcnt.ensure((elem + 1) * 4);   // (the batch kernels' only reader is ts_goto's version pass, compiled out by default: ADVICE r4)
       b_it.ensure((leaves + 1) * (span ? (size_t)SP_REC : 256) * 4);
       b_dir_out.ensure((leaves + 1) * 4);
@@ -1158,7 +1162,7 @@ struct Engine {
     b_ht0.ensure((size_t)n_docs * 8); b_ht_cap.ensure((size_t)n_docs * 4); b_ht_cnt.ensure((size_t)n_docs * 4 + 4);
     lmbe::h2d(b_ht0.p, h_ht0.data(), (size_t)n_docs * 8);
     lmbe::h2d(b_ht_cap.p, h_ht_cap.data(), (size_t)n_docs * 4);
-    d.cp = b_cp.as<uint32_t>(); d.loc = b_loc.as<uint32_t>(); d.dcnt = ((resident || (LM_BATCH_VSWEEP && want_dcnt && span)) && kn.version_sweep) ? b_dcnt.as<uint32_t>() : nullptr; d.tb = b_tb.as<uint8_t>();
+    d.cp = b_cp.as<uint32_t>(); d.loc = b_loc.as<uint32_t>(); d.kept = b_kept.as<uint32_t>(); d.dcnt = ((resident || (LM_BATCH_VSWEEP && want_dcnt && span)) && kn.version_sweep) ? b_dcnt.as<uint32_t>() : nullptr; d.tb = b_tb.as<uint8_t>();
     d.it = b_it.as<uint32_t>();
     d.dir_out = b_dir_out.as<uint32_t>();
     d.lf_chunk = b_lf_chunk.as<uint8_t>();
@@ -1167,10 +1171,10 @@ struct Engine {
     d.ht0 = b_ht0.as<uint64_t>(); d.ht_cap = b_ht_cap.as<uint32_t>();
     d.ht_list = b_ht_list.as<uint32_t>(); d.ht_cnt = b_ht_cnt.as<uint32_t>();
     lmbe::dmemset(b_ht_cnt.p, 0, (size_t)n_docs * 4 + 4);
-    // loc[] := NONE.  A batch: one memset on the stream, in front of the payload fill — it runs beside the other stream's /
-    // context's issue-bound integrate kernel instead of inside this one (LM_LOC_MEMSET=0: every document's wave clears its own
-    // slice, as resident documents always do — they keep loc[] between runs).  cp[] needs no fill: every element that can be
-    // placed was written by k_elem_fill
+    // kept[] := 0 (the bitmap of loc[]'s kept entries; loc[] itself is not cleared — lm_k_integrate_span.h sp_keep).  A batch: one
+    // fill on the stream, in front of the payload fill (LM_LOC_MEMSET=0: every document's wave clears its own slice, as resident
+    // documents always do — they keep loc[] and kept[] between runs).  The kernels that want a dense loc[] clear their documents'
+    // slices themselves.  cp[] needs no fill: every element that can be placed was written by k_elem_fill
     d.loc_cleared = (!resident && span && kn.loc_memset) ? 1u : 0u;
     d.no_linear = kn.linear && !keep_tombstones ? 0u : 1u;
     d.posdel_redo = (kn.redo && kn.posdel && st_valid && (resident ? shared_mode != 0 : !span)) ? 1u : 0u;
@@ -1201,9 +1205,19 @@ struct Engine {
       // (k_fill_words, not hipMemsetAsync: its fill kernel writes at half of what HBM takes; the buffers are padded to 16 bytes.  Clearing
       // speculatively on a second stream beside the decode stage — as many words as the last run needed, joined here — was built and
       // measured: the step got SLOWER, 23.0 against 22.7 ms (k_frame_count 0.30 -> 0.72 ms under the 2 GB of stores; profiles/r06_side_fill_ab.log))
-      const uint64_t n4 = ((uint64_t)elem + 3) / 4;
+      const uint64_t n4 = ((uint64_t)elem / 32 + 3) / 4;
       const uint32_t blocks = (uint32_t)std::min<uint64_t>((n4 + 255) / 256, 4096);
-      LM_LAUNCH(k_fill_words, blocks, 256, b_loc.as<uint32_t>(), n4, NONE, blocks * 256u);
+      LM_LAUNCH(k_fill_words, blocks, 256, b_kept.as<uint32_t>(), n4, 0u, blocks * 256u);
+    }
+    if (kn.loc_poison && span && (resident ? elem_top : elem)) {
+      // LM_LOC_POISON=1 (tests): loc[] := 0, a valid leaf number of every document — a read of an entry whose bit is clear then shows as
+      // wrong bytes or LM_INTERNAL, never as an address outside the document's leaf pool.  (Resident: every entry whose bit is clear NOW,
+      // in front of the integrate stage's own clears — a document that is about to be rebuilt keeps the previous run's entries, stale leaf
+      // numbers under bits that the rebuild clears: as good a poison.)
+      const uint64_t n = resident ? elem_top : elem, n4 = (n + 3) / 4;
+      const uint32_t blocks = (uint32_t)std::min<uint64_t>(((resident ? n : n4) + 255) / 256, 4096);
+      if (resident) LM_LAUNCH(k_fill_unkept, blocks, 256, b_loc.as<uint32_t>(), b_kept.as<uint32_t>(), n, 0u, blocks * 256u);
+      else LM_LAUNCH(k_fill_words, blocks, 256, b_loc.as<uint32_t>(), n4, 0u, blocks * 256u);
     }
     if (ht) { lmbe::dmemset(b_ht_key.p, 0xff, ht * 8); lmbe::dmemset(b_ht_best.p, 0, ht * 8); }
       if (resident) {

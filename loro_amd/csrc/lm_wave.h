@@ -47,6 +47,8 @@ LM_DEV uint32_t atomic_max32(uint32_t* p, uint32_t v) { return atomicMax(p, v); 
 LM_DEV void lds_add(uint32_t* p, uint32_t v) { (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 LM_DEV uint64_t atomic_max64(unsigned long long* p, uint64_t v) { return atomicMax(p, (unsigned long long)v); }
 LM_DEV uint32_t atomic_or(uint32_t* p, uint32_t v) { return atomicOr(p, v); }
+// a word other lanes change with device atomics (they execute at L2): read there, never from a line of the CU's vector cache
+LM_DEV uint32_t load_agent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 LM_DEV uint64_t atomic_cas64(unsigned long long* p, uint64_t cmp, uint64_t v) {
   return atomicCAS(p, (unsigned long long)cmp, (unsigned long long)v);
 }
@@ -58,6 +60,7 @@ LM_DEV int ffs64(uint64_t m) { return __ffsll((unsigned long long)m) - 1; }  // 
 LM_DEV void wave_sync() { __builtin_amdgcn_wave_barrier(); }
 LM_DEV void mem_fence() { __threadfence(); }   // global stores of this wave are visible to later loads of any lane
 LM_DEV uint64_t clock() { return __builtin_readcyclecounter(); }
+LM_DEV void emu_note_lookup(const uint32_t*, uint32_t, uint32_t) {}   // (harness only, below)
 }  // namespace lmw
 
 #else  // ------------------------------------------------------------------ LM_EMU (tests only)
@@ -65,6 +68,7 @@ LM_DEV uint64_t clock() { return __builtin_readcyclecounter(); }
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include <map>
 #include <functional>
 #include <ucontext.h>
 #define LM_DEV inline
@@ -277,12 +281,33 @@ inline uint32_t atomic_max32(uint32_t* p, uint32_t v) { uint32_t o = *p; if (v >
 inline void lds_add(uint32_t* p, uint32_t v) { *p += v; }
 inline uint64_t atomic_max64(unsigned long long* p, uint64_t v) { uint64_t o = *p; if (v > o) *p = v; return o; }
 inline uint32_t atomic_or(uint32_t* p, uint32_t v) { uint32_t o = *p; *p = o | v; return o; }
+inline uint32_t load_agent(const uint32_t* p) { return *p; }
 inline uint64_t atomic_cas64(unsigned long long* p, uint64_t cmp, uint64_t v) { uint64_t o = *p; if (o == cmp) *p = v; return o; }
 inline int popc64(uint64_t m) { return __builtin_popcountll(m); }
 inline int ffs64(uint64_t m) { return m ? __builtin_ctzll(m) : -1; }
 inline void wave_sync() { (void)emu_exchange(0); }
 inline void mem_fence() {}
 inline uint64_t clock() { return 0; }
+// A lookup of the `width` slots from `slot0` on of a bitmap (lm_k_integrate_span.h ts_loc_find).  Counted for the tests: [0] lookups,
+// [1] lookups of a window whose bits changed since its previous lookup; lmemu_loc_stat(-1) starts over.
+struct EmuLookups { uint64_t n[2]; std::map<std::pair<const uint32_t*, uint32_t>, uint64_t> seen; };
+inline EmuLookups& emu_lookups() { static EmuLookups s; return s; }
+inline void emu_note_lookup(const uint32_t* bits, uint32_t slot0, uint32_t width) {
+  if (lane() != 0) return;
+  EmuLookups& s = emu_lookups();
+  uint64_t w = 0;
+  for (uint32_t i = 0; i < width; i++) w |= (uint64_t)((bits[(slot0 + i) >> 5] >> ((slot0 + i) & 31)) & 1u) << i;
+  auto key = std::make_pair(bits, slot0);
+  auto it = s.seen.find(key);
+  s.n[0]++;
+  if (it != s.seen.end() && it->second != w) s.n[1]++;
+  s.seen[key] = w;
+}
+extern "C" __attribute__((used, visibility("default"))) inline uint64_t lmemu_loc_stat(int i) {
+  EmuLookups& s = emu_lookups();
+  if (i < 0) { s.n[0] = s.n[1] = 0; s.seen.clear(); return 0; }
+  return s.n[i & 1];
+}
 }  // namespace lmw
 #endif
 
