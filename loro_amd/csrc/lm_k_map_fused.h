@@ -16,7 +16,9 @@
 //     below 0x20 is not, so the candidates (bytes < 0x20) are ranked by one wave scan per step, and accepted only when every
 //     candidate's successor is candidate + 1 + length — which makes the candidates the chain (induction from offset 0).  Keys of 32
 //     bytes or more, or with control characters, take the general path: every lane works out where the key that would start at ITS
-//     byte ends, and the chain hops from start to start through v_readlane (no memory round trip per key);
+//     byte ends, and the chain hops from start to start through v_readlane (no memory round trip per key).  The candidates are COUNTED
+//     against MF_KMAX before they are verified: a table with more than MF_KMAX bytes below 0x20 is handed over (DF_REDO), not walked
+//     by the general path, however few keys it holds (300 keys of four tabs each: tests/_merge_docs_map.py);
 //   * the key-index column (prop, DeltaRle): a literal segment is cut at its varint terminators — rank by the same scan — and
 //     decoded by the lane that holds the terminator; runs are filled by arithmetic; one more pass turns deltas into indices.  The
 //     other three columns (container_index, value_type, len) are runs in practice: read once when they are, 64 rows at a time otherwise;
@@ -576,7 +578,7 @@ LM_KERNEL LM_WAVES_PER_SIMD(4) void k_map_fused(Dev d, DevMf f, uint32_t* retry_
         const uint32_t incl = lmw::scan_incl_add(ncl);
         uint32_t rk = nk + incl - ncl;
         const uint32_t tot = lmw::bcast(incl, 63);
-        if (nk + tot > MF_KMAX) { fastk = false; bail = true; break; }
+        if (nk + tot > MF_KMAX) { fastk = false; bail = true; break; }   // (CANDIDATES, counted before they are verified: a table of fewer keys with more than MF_KMAX control characters in them is handed over too)
 #pragma unroll
         for (int q = 0; q < 4; q++) if ((cand >> q) & 1u) { kpos[rk] = (uint16_t)(o + q); rk++; }
         nk += tot;

@@ -58,7 +58,17 @@ ITEMS; an ELEMENT is named by the IdLp (peer, lamport) of the insert atom that m
 
 Checkout: the same functions over the closure of the given frontiers.
 
-NOT modelled: Tree, Counter, pending changes (a change whose deps are missing), damaged input, snapshot state sections.
+Pending changes (oplog/pending_changes.rs; `Model(changes, delivered=…)`).  Of the changes that were DELIVERED a change applies iff
+its peer's previous counter is applied (or it starts at 0) and every id it depends on lies in an applied change — the least fixpoint
+of that rule, whatever the order of delivery.  The value and the version vector come from the applied changes only; the fourth element
+of `result()` is the number of atoms delivered but not applied.  Pending does NOT depend on the checked-out version: the whole
+history is imported first and the checkout follows (loro.rs import, then checkout), so a checkout of the applied part reports the
+same count as the latest version.  Scope: no pending change is delivered twice (its atoms would be
+counted once here) — duplicate only blobs that apply; the applied end of a peer lies on an op boundary of the writers' changes.
+
+Map outcomes (`Model.map_outcomes`): what the LWW rule had to decide in this history, counted from the entries and the closures alone.
+
+NOT modelled: Tree, Counter, damaged input, snapshot state sections.
 """
 from _values import to_json
 from loro_amd import wire
@@ -66,6 +76,9 @@ from loro_amd import wire
 OUTCOMES = ("inserts", "between", "foreign_left_break", "same_right_break", "same_right_pass", "diff_right_less", "diff_right_greater",
             "diff_right_equal")
 # what the element rules of a MovableList decided, at the latest version (Model.movable_outcomes)
+# what the LWW rule of a Map decided (Model.map_outcomes)
+MAP_OUTCOMES = ("concurrent_keys", "tie_on_lamport", "tie_won_by_last_delivered", "tie_won_by_first_delivered", "winner_is_delete",
+                "child_map_hidden", "checkout_winner_differs")
 MOVABLE_OUTCOMES = ("concurrent_moves", "winner_has_smaller_peer", "move_tie_on_lamport", "loser_item_alive", "winner_deleted_loser_alive",
                     "concurrent_sets", "set_tie_on_lamport")
 
@@ -184,8 +197,47 @@ def _place(els, P, pos, id, what, stats):
     els.insert(insert_at, Elem(id, origin_left, origin_right, what))
 
 
+def applied_ends(delivered):
+    """peer -> first counter that is NOT applied, of the delivered changes (anything with peer / counter / ctr_end / deps): the least
+    fixpoint of "its peer's previous counter is applied or it starts at 0, and every dep id lies in an applied change" """
+    end = {}
+    todo = list(delivered)
+    progress = True
+    while progress:
+        progress = False
+        rest = []
+        for c in todo:
+            have = end.get(c.peer, 0)
+            if c.ctr_end <= have:
+                continue                                    # known already: dropped
+            if c.counter <= have and all(end.get(p, 0) > k for p, k in c.deps):
+                end[c.peer] = c.ctr_end                     # (a change that overlaps the applied end is sliced: its tail applies)
+                progress = True
+            else:
+                rest.append(c)
+        todo = rest
+    return end
+
+
+def _cut(ch, end):
+    """the ops of `ch` below the applied end `end` of its peer (an op boundary)"""
+    if ch.ctr_end <= end:
+        return ch
+    ops = [o for o in ch.ops if o.counter + o.atom_len <= end]
+    assert ops and ops[-1].counter + ops[-1].atom_len == end, ("the applied end of a peer cuts an op", ch.peer, end)
+    return wire.Change(ch.peer, ch.counter, ch.lamport, list(ch.deps), ops, timestamp=ch.timestamp, msg=ch.msg)
+
+
 class Model:
-    def __init__(self, changes):
+    def __init__(self, changes, delivered=None):
+        """`changes`: the writers' changes.  `delivered`: the changes the document's blobs hold, when they are not all of them"""
+        self.pending = 0
+        if delivered is not None:
+            delivered = list(delivered)
+            end = applied_ends(delivered)
+            ids = {(c.peer, k) for c in delivered for k in range(c.counter, c.ctr_end)}
+            self.pending = sum(1 for p, k in ids if k >= end.get(p, 0))
+            changes = [_cut(c, end[c.peer]) for c in changes if c.counter < end.get(c.peer, 0)]
         self.changes = sorted(changes, key=lambda c: (c.lamport, c.peer, c.counter))
         self.by_peer = {}
         for c in self.changes:
@@ -230,12 +282,12 @@ class Model:
     def _apply(self, ch):
         base = self.below(ch)
         for op in ch.ops:
-            P = base | {(ch.peer, k) for k in range(ch.counter, op.counter)}
             lam = ch.lamport + op.counter - ch.counter
-            if op.kind in ("map_set", "map_delete"):
+            if op.kind in ("map_set", "map_delete"):      # (a Map write needs no version: its entry competes wherever it is seen)
                 self.maps.setdefault(op.cid, {}).setdefault(op.key, []).append(
                     (lam, ch.peer, (ch.peer, op.counter), op.value if op.kind == "map_set" else _GONE))
                 continue
+            P = base | {(ch.peer, k) for k in range(ch.counter, op.counter)}
             els = self.seqs.setdefault(op.cid, [])
             if op.cid.kind == wire.KIND_MOVABLE and op.kind != "delete":
                 self._apply_movable(ch, op, P, lam, els)
@@ -314,6 +366,48 @@ class Model:
             tot["loser_item_alive"] += sum(1 for id in alive if id not in pointed)
         return tot
 
+    def map_winner(self, cid, key, V):
+        """the winning entry (lamport, peer, op id, value) of a key at the version V, None if V holds no write to it"""
+        seen = [e for e in self.maps[cid][key] if e[2] in V]
+        return max(seen, key=lambda e: (e[0], e[1])) if seen else None
+
+    def map_pairs(self, frontiers=None):
+        """the number of distinct (Map, key) pairs the version holds a write to"""
+        V = self.version(frontiers)
+        return sum(1 for keys in self.maps.values() for entries in keys.values() if any(e[2] in V for e in entries))
+
+    def map_outcomes(self, delivery=(), versions=()):
+        """MAP_OUTCOMES, per (Map, key), at the latest version.  concurrent_keys: the closure of the winner's id does not hold another
+        write to the key (the rule, not causality, decided); tie_on_lamport: one of those has the winner's lamport (the peer id
+        decided); tie_won_by_last_delivered / _first_delivered: `delivery` lists the peers in the order their blobs are delivered, and
+        the winner of such a tie comes after / before every peer it tied with; winner_is_delete; child_map_hidden: per child Map whose
+        creating write lost to a write that had not seen it; checkout_winner_differs: at one of `versions` (frontiers) the key has a
+        winner, and it is not the latest one."""
+        tot = dict.fromkeys(MAP_OUTCOMES, 0)
+        rank = {p: i for i, p in enumerate(delivery)}
+        Vs = [self.version(fr) for fr in versions]
+        for cid, keys in self.maps.items():
+            for key, entries in keys.items():
+                win = self.map_winner(cid, key, self.all_ids)
+                below = self.closure_of_id(win[2])
+                others = [e for e in entries if e[2] != win[2] and e[2] not in below]
+                if others:
+                    tot["concurrent_keys"] += 1
+                    tied = [e for e in others if e[0] == win[0]]
+                    if tied:
+                        tot["tie_on_lamport"] += 1
+                        if win[1] in rank and all(e[1] in rank for e in tied):
+                            tot["tie_won_by_last_delivered"] += all(rank[win[1]] > rank[e[1]] for e in tied)
+                            tot["tie_won_by_first_delivered"] += all(rank[win[1]] < rank[e[1]] for e in tied)
+                tot["winner_is_delete"] += win[3] is _GONE
+                tot["child_map_hidden"] += sum(1 for e in others if isinstance(e[3], wire.ContainerValue) and e[3].kind == wire.KIND_MAP)
+                for V in Vs:
+                    w = self.map_winner(cid, key, V)
+                    if w is not None and w[2] != win[2]:
+                        tot["checkout_winner_differs"] += 1
+                        break
+        return tot
+
     # ---- reading
     def visible_ids(self, cid, frontiers=None):
         V = self.version(frontiers)
@@ -379,7 +473,7 @@ class Model:
 
     def result(self, frontiers=None):
         """(status, json, vv, pending) as merge_batch returns it"""
-        return (0, self.json(frontiers), self.vv(frontiers), 0)
+        return (0, self.json(frontiers), self.vv(frontiers), self.pending)
 
 
 _GONE = object()
