@@ -402,6 +402,43 @@ int lm_delta(lm_ctx* ctx, const lm_delta_query* queries, size_t n, int units, lm
  * packed on the device (each rounded up to 16 bytes) — proportional to the change, never to the documents. */
 uint64_t lm_delta_bytes(lm_ctx* ctx);
 
+/* ---- Map deltas from a version to the rendered one: what LoroDoc::diff(a, b) and the MapDelta events of subscribe tell a subscriber
+ * about the Map containers (diff_calc.rs:545-610 over get_container_latest_op_at_vv), answered on the device from the LWW tables and
+ * op rows of the last lm_run (k_mdelta_mark, k_mdelta: loro_amd/csrc/lm_k_delta_map.h).  Same query and result structs as lm_delta,
+ * no `units`; valid in the same states, the same -1 for a call that cannot be answered, the same batch shapes.  A = from_vv, V = the
+ * version that run rendered (the latest version, the entry's checkout, a resident document's state).
+ *
+ * Definition.  For one Map container and one key a WRITE is a Map set or Map delete op of an applied change (beyond a sliced
+ * change's known prefix).  The winner at a version X is the write with the greatest (lamport, peer id) among the writes whose id
+ * lies in X (counter < X[peer]); "no write in X" is a state of its own, distinct from a winning delete.  With wA / wV the winners
+ * at A / V:
+ *   - wV absent: nothing (cannot be when A is contained in V and something is reported);
+ *   - wA and wV are the same op: nothing;
+ *   - wA absent: reported — wV a set goes to "updated", wV a delete to "deleted" (the reference pushes every key that is only in
+ *     the target map, a delete included);
+ *   - both deletes: nothing; exactly one a delete: reported;
+ *   - both sets: reported iff the values differ under LoroValue equality (loro-common/src/value.rs:29-44): different kinds differ
+ *     (I64 3 against F64 3.0); Null, Bool, I64 by value; F64 as a == b || (a.is_nan() && b.is_nan()), so 0.0 equals -0.0 although
+ *     their JSON differs; String and Binary by bytes; a child container is the ContainerID of its creating op, two ops are never
+ *     equal.  Two nested List values, or two nested Map values, from different ops are NOT decided on the device (nested Map values
+ *     name keys through their block's key table; JSON equality parts from LoroValue equality on +-0.0 and Binary against List):
+ *     the key is left out and bit 1 of other_changed is set — the right value or a refusal, never a guess.
+ * other_changed of this call: bit 0 — an op with an id in V \ A went to a MovableList, Tree or Counter container; bit 1 — an
+ * undecided nested pair.  Text and List ops set nothing (lm_delta covers them).
+ * Result bytes of a query: one JSON object over every Map container of the document whose delta is not empty — decided by id sets: a
+ * child Map hidden by a later write to its parent's key is still listed under its own ContainerID —
+ *   {"<ContainerID Display>":{"updated":{"<key>":<value>,...},"deleted":["<key>",...]},...}
+ * both members always present; keys inside "updated" and "deleted" in the bytewise order of their raw bytes (lm_fetch's order),
+ * escaped as lm_fetch escapes them; values in lm_fetch's canonical form; a child container is the parrot string (U+1F99C ':'
+ * ContainerID Display) as in lm_delta, its content stands under its own key; containers in the bytewise order of their JSON-encoded
+ * keys; {} when nothing changed.
+ * Statuses: lm_delta's.  LM_UNSUPPORTED also when the kernel's self-check failed: the winner at V found from the op rows must equal
+ * the winner the run's LWW stage left in the document's table, for every key.  A document that was decoded without op rows (an LWW
+ * Map document, lm_fused_documents) is run once more through the row tables first; lm_fetch gives the same bytes afterwards.
+ * lm_delta_bytes reports the bytes of whichever of lm_delta / lm_delta_map ran last; `json` is valid until the next lm_delta /
+ * lm_delta_map / lm_stage / lm_destroy.  The call changes nothing a run wrote. */
+int lm_delta_map(lm_ctx* ctx, const lm_delta_query* queries, size_t n, lm_delta_result* out);
+
 /* Wave-primitive self test on the device (DPP scan, ballot ranks); returns the number of mismatches. */
 int lm_selftest(lm_ctx* ctx);
 

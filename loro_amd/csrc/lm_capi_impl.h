@@ -294,7 +294,7 @@ struct lm_ctx_impl {
     mapped = false;
     rd.on = false;
     sum_rows_padded = 0;             // (a new batch: lm_summary_layout is called again for it)
-    for (auto& pt : parts) { pt->sum_rows = nullptr; pt->keep_tombstones = false; }
+    for (auto& pt : parts) { pt->sum_rows = nullptr; pt->keep_tombstones = false; pt->no_map_fused = false; }
     dl_json.clear();
     // split into contiguous ranges of about equal blob bytes; small batches stay in one part
     uint64_t total = 0;
@@ -566,8 +566,28 @@ struct lm_ctx_impl {
   // that hold their documents as cursor() routes them
   uint64_t dl_d2h_bytes = 0;                   // … and the bytes that call copied back from the device (result rows + packed JSON)
   std::vector<std::vector<uint8_t>> dl_json;   // the bytes of the last lm_delta's results: valid until the next lm_delta / lm_stage / lm_destroy
-  void delta(std::vector<lm::Engine::DeltaIn>& in, int units, std::vector<lm::Engine::DeltaOut>& out) {
-    cursor_prepare("lm_delta");
+  void delta(std::vector<lm::Engine::DeltaIn>& in, int units, std::vector<lm::Engine::DeltaOut>& out) { delta_route("lm_delta", in, out, [&](lm::Engine& e, const std::vector<lm::Engine::DeltaIn>& sub, std::vector<lm::Engine::DeltaOut>& r) { e.delta(sub, units, r); }); }
+  // ---- lm_delta_map (lm_k_delta_map.h): routed like lm_delta.  A queried document that was decoded without op rows (k_map_fused) has
+  // nothing the call could read: its part is run once more through the row tables — the same bytes out — and stays there until the
+  // next lm_stage
+  void delta_map(std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& out) {
+    cursor_prepare("lm_delta_map");
+    bool any = false;
+    for (size_t k = 0; k < in.size(); k++) {
+      const size_t doc = in[k].doc;
+      if (redone(doc)) continue;
+      uint32_t p = 0, local = 0;
+      if (mapped) { p = emap[doc].first; local = emap[doc].second; }
+      else { while (p + 1 < n_parts() && doc >= first[p + 1]) p++; local = (uint32_t)(doc - first[p]); }
+      lm::Engine& e = *parts[p];
+      if (!e.no_map_fused && local < e.h_fused.size() && e.h_fused[local]) { e.no_map_fused = true; any = true; }
+    }
+    if (any) { run(); sum_host_rows(); }
+    delta_route(nullptr, in, out, [&](lm::Engine& e, const std::vector<lm::Engine::DeltaIn>& sub, std::vector<lm::Engine::DeltaOut>& r) { e.delta_map(sub, r); });
+  }
+  // `prepare`: the call's name for cursor_prepare, nullptr when the caller has done that
+  template <class F> void delta_route(const char* prepare, std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& out, F call) {
+    if (prepare) cursor_prepare(prepare);
     out.assign(in.size(), lm::Engine::DeltaOut());
     std::vector<std::vector<uint32_t>> of(n_parts() + 1);   // the queries of every part; the last list is the side engine's
     for (size_t k = 0; k < in.size(); k++) {
@@ -587,7 +607,7 @@ struct lm_ctx_impl {
       e.profiling = profiling != 0;
       sub.clear();
       for (uint32_t k : of[p]) sub.push_back(in[k]);
-      e.delta(sub, units, r);
+      call(e, sub, r);
       dl_d2h_bytes += e.dl_d2h_bytes;
       for (size_t j = 0; j < of[p].size(); j++) out[of[p][j]] = std::move(r[j]);
       if (profiling) for (auto& kt : e.dl_times) times.push_back(kt);
@@ -967,6 +987,28 @@ int LM_API(delta)(void* c, const lm_delta_query_c* qs, size_t n, int units, lm_d
     }
     std::vector<lm::Engine::DeltaOut> r;
     x->delta(in, units, r);
+    x->dl_json.resize(n);
+    for (size_t k = 0; k < n; k++) {
+      x->dl_json[k].swap(r[k].json);
+      x->dl_json[k].push_back(0);   // (never an empty vector: json is a valid pointer for every query)
+      out[k].status = r[k].status; out[k].other_changed = r[k].other_changed;
+      out[k].json = x->dl_json[k].data(); out[k].json_len = x->dl_json[k].size() - 1;
+    }
+    return 0;
+  } catch (const std::exception& e) { x->err = e.what(); return -1; }
+}
+// ---- Map deltas from a version to the rendered one (include/loro_merge.h): on the device, from the LWW tables and op rows of the
+// last lm_run (lm_k_delta_map.h)
+int LM_API(delta_map)(void* c, const lm_delta_query_c* qs, size_t n, lm_delta_result_c* out) {
+  auto* x = (lm_ctx_impl*)c;
+  try {
+    std::vector<lm::Engine::DeltaIn> in(n);
+    for (size_t k = 0; k < n; k++) {
+      if (qs[k].doc >= x->api_docs()) throw std::runtime_error("lm_delta_map: no such document");
+      in[k].doc = (uint32_t)qs[k].doc; in[k].vv = qs[k].from_vv; in[k].vv_len = qs[k].from_vv ? qs[k].from_vv_len : 0;
+    }
+    std::vector<lm::Engine::DeltaOut> r;
+    x->delta_map(in, r);
     x->dl_json.resize(n);
     for (size_t k = 0; k < n; k++) {
       x->dl_json[k].swap(r[k].json);

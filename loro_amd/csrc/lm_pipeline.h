@@ -26,6 +26,7 @@
 #include "lm_k_richtext.h"
 #include "lm_k_cursor.h"
 #include "lm_k_delta.h"
+#include "lm_k_delta_map.h"
 #include "lm_snapshot.h"
 #include "lm_export.h"
 #include "lm_snapshot_base.h"
@@ -130,6 +131,7 @@ struct Engine {
   int rt_launches = 0;                            // k_richtext / k_richtext_walk launches of the last lm_richtext (1; + 1: style values that need the walk; + 1: a slab was too small)
   // lm_cursor_pos / lm_cursor_at (lm_k_cursor.h)
   DBuf b_cur_doc, b_cur_dg, b_cur_grp, b_cur_q, b_cur_names, b_cur_res;
+  bool no_map_fused = false;                      // the next runs decode every LWW Map document through the row tables (lm_delta_map needs its op rows)
   bool keep_tombstones = false;                   // the next runs replay without the linear prefix (it drops what it deletes from the leaves: cursor_needs_tombstones)
   double cur_ms = 0;                              // k_cursor of the last call (profiling)
   // lm_delta (lm_k_delta.h)
@@ -922,7 +924,7 @@ struct Engine {
     // while the side engine can take a document the fused kernel gives up on (DF_REDO)
     n_fused = 0;
     h_fused.assign(n_docs, 0);
-    const bool mf_on = kn.map_fused && kn.redo && kn.lww_lds && kn.ht_opt && kn.ht_opt <= LWW_LDS_CAP && !resident && st_valid && NB;
+    const bool mf_on = kn.map_fused && !no_map_fused && kn.redo && kn.lww_lds && kn.ht_opt && kn.ht_opt <= LWW_LDS_CAP && !resident && st_valid && NB;
     if (mf_on) {
       b_blk_kind.ensure((size_t)(NB + 1) * 4); b_doc_fused.ensure((size_t)n_docs + 16);
       d.blk_kind = b_blk_kind.as<uint32_t>();
@@ -1855,6 +1857,48 @@ struct Engine {
     }
     return at == n;
   }
+  // what lm_delta and lm_delta_map share: the document's peer table and the version the run rendered (once per call and document), the
+  // query's from_vv parsed and mapped to per-peer-index bounds.  false: `o` is the query's answer (a status); true: a[] = A per peer index, dip = the document's peers and V
+  struct DeltaDoc { std::vector<uint64_t> peers; std::vector<uint32_t> V; int32_t status = ST_OK; };
+  bool delta_bounds(const DeltaIn& q, const char* who, std::map<uint32_t, DeltaDoc>& info, std::vector<uint8_t>& buf, DeltaOut& o, std::vector<uint32_t>& a, const DeltaDoc*& dip) {
+    const uint32_t doc = q.doc;
+    if (doc >= n_docs) throw std::runtime_error(std::string(who) + ": no such document");
+    const DocMeta& m = h_doc[doc];
+    if (m.status != ST_OK) { o.status = m.status; return false; }
+    if (m.flags & DF_FRONT_ERR) { o.status = m.front_err; return false; }
+    std::map<uint64_t, int64_t> A;
+    if (!delta_parse_vv(q.vv, q.vv_len, A)) { o.status = ST_DECODE_ERROR; return false; }
+    auto it = info.find(doc);
+    if (it == info.end()) {   // the document's peer table and the version the run rendered, once per call
+      DeltaDoc di;
+      di.peers.resize(m.n_peers);
+      di.V.assign(m.n_peers, 0);
+      if (m.n_peers) lmbe::d2h(di.peers.data(), b_peer_uniq.as<uint64_t>() + m.praw0, (size_t)m.n_peers * 8);
+      buf.resize(m.vv_len);
+      if (m.vv_len) lmbe::d2h(buf.data(), b_vv_out.as<uint8_t>() + h_vv_off[doc], m.vv_len);
+      lmbe::sync();
+      std::map<uint64_t, int64_t> V;
+      if (m.n_peers > MAX_PEERS || !delta_parse_vv(buf.data(), buf.size(), V)) di.status = ST_UNSUPPORTED;
+      for (auto& kv : V) {
+        auto pi = std::lower_bound(di.peers.begin(), di.peers.end(), kv.first);
+        if (kv.second <= 0) continue;
+        if (pi == di.peers.end() || *pi != kv.first) { di.status = ST_UNSUPPORTED; break; }   // (a version the op rows do not span: no rendering from ids)
+        di.V[pi - di.peers.begin()] = (uint32_t)kv.second;
+      }
+      it = info.emplace(doc, std::move(di)).first;
+    }
+    const DeltaDoc& di = it->second;
+    dip = &di;
+    if (di.status != ST_OK) { o.status = di.status; return false; }
+    a.assign(m.n_peers, 0);
+    for (auto& kv : A) {
+      if (kv.second <= 0) continue;
+      auto pi = std::lower_bound(di.peers.begin(), di.peers.end(), kv.first);
+      if (pi == di.peers.end() || *pi != kv.first || (uint64_t)kv.second > di.V[pi - di.peers.begin()]) { o.status = ST_FRONTIERS_NOT_FOUND; return false; }
+      a[pi - di.peers.begin()] = (uint32_t)kv.second;
+    }
+    return true;
+  }
   void delta(const std::vector<DeltaIn>& in, int units, std::vector<DeltaOut>& out) {
     lmbe::bind(sc);
     if (!ran) throw std::runtime_error("lm_delta before lm_run");
@@ -1862,8 +1906,7 @@ struct Engine {
     out.assign(in.size(), DeltaOut());
     dl_times.clear();
     dl_launches = 0;
-    struct DocInfo { std::vector<uint64_t> peers; std::vector<uint32_t> V; int32_t status = ST_OK; };
-    std::map<uint32_t, DocInfo> info;
+    std::map<uint32_t, DeltaDoc> info;
     std::vector<uint32_t> idx, bnd;
     std::vector<DlQuery> qs;
     std::vector<uint64_t> off(1, 0);
@@ -1874,43 +1917,12 @@ struct Engine {
     std::vector<uint8_t> buf;
     for (size_t k = 0; k < in.size(); k++) {
       const uint32_t doc = in[k].doc;
-      if (doc >= n_docs) throw std::runtime_error("lm_delta: no such document");
-      const DocMeta& m = h_doc[doc];
       DeltaOut& o = out[k];
-      if (m.status != ST_OK) { o.status = m.status; continue; }
-      if (m.flags & DF_FRONT_ERR) { o.status = m.front_err; continue; }
-      std::map<uint64_t, int64_t> A;
-      if (!delta_parse_vv(in[k].vv, in[k].vv_len, A)) { o.status = ST_DECODE_ERROR; continue; }
-      auto it = info.find(doc);
-      if (it == info.end()) {   // the document's peer table and the version the run rendered, once per call
-        DocInfo di;
-        di.peers.resize(m.n_peers);
-        di.V.assign(m.n_peers, 0);
-        if (m.n_peers) lmbe::d2h(di.peers.data(), b_peer_uniq.as<uint64_t>() + m.praw0, (size_t)m.n_peers * 8);
-        buf.resize(m.vv_len);
-        if (m.vv_len) lmbe::d2h(buf.data(), b_vv_out.as<uint8_t>() + h_vv_off[doc], m.vv_len);
-        lmbe::sync();
-        std::map<uint64_t, int64_t> V;
-        if (m.n_peers > MAX_PEERS || !delta_parse_vv(buf.data(), buf.size(), V)) di.status = ST_UNSUPPORTED;
-        for (auto& kv : V) {
-          auto pi = std::lower_bound(di.peers.begin(), di.peers.end(), kv.first);
-          if (kv.second <= 0) continue;
-          if (pi == di.peers.end() || *pi != kv.first) { di.status = ST_UNSUPPORTED; break; }   // (a version the op rows do not span: no rendering from ids)
-          di.V[pi - di.peers.begin()] = (uint32_t)kv.second;
-        }
-        it = info.emplace(doc, std::move(di)).first;
-      }
-      const DocInfo& di = it->second;
-      if (di.status != ST_OK) { o.status = di.status; continue; }
-      std::vector<uint32_t> a(m.n_peers, 0);
-      bool inside = true;
-      for (auto& kv : A) {
-        if (kv.second <= 0) continue;
-        auto pi = std::lower_bound(di.peers.begin(), di.peers.end(), kv.first);
-        if (pi == di.peers.end() || *pi != kv.first || (uint64_t)kv.second > di.V[pi - di.peers.begin()]) { inside = false; break; }
-        a[pi - di.peers.begin()] = (uint32_t)kv.second;
-      }
-      if (!inside) { o.status = ST_FRONTIERS_NOT_FOUND; continue; }
+      std::vector<uint32_t> a;
+      const DeltaDoc* dip = nullptr;
+      if (!delta_bounds(in[k], "lm_delta", info, buf, o, a, dip)) continue;
+      const DocMeta& m = h_doc[doc];
+      const DeltaDoc& di = *dip;
       if (doc < h_fused.size() && h_fused[doc]) {   // an LWW Map document decoded without op rows: Maps only
         for (uint32_t p = 0; p < m.n_peers; p++) if (di.V[p] > a[p]) o.other_changed = 1u;
         o.json = {'{', '}'};
@@ -1943,21 +1955,30 @@ struct Engine {
     lmbe::dmemset(b_dl_bits.p, 0, (words + 1) * 4);
     lmbe::dmemset(b_dl_res.p, 0, nq * sizeof(DlRes));
     Dev d = last_d;
-    std::vector<DlRes> r(nq);
     lmbe::reset_times();
     if (blocks) {
       lmbe::tic(profiling);
       LM_LAUNCH(k_delta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (uint32_t)nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_res.as<DlRes>());
       lmbe::toc("k_delta_mark", dl_times, profiling);
     }
+    delta_slabs(off, idx, out, false, [&]() {
+      LM_LAUNCH(k_delta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), (const uint32_t*)b_dl_bits.as<uint32_t>(), b_dl_out.as<uint8_t>(),
+                (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>(), units);
+      lmbe::toc("k_delta", dl_times, profiling);
+    });
+  }
+  // the second half of lm_delta / lm_delta_map: `launch` renders the queries into the slabs of `off` (it closes its own timing), once
+  // more at exact sizes when a slab was too small; then the written bytes are packed, copied back and handed to the queries' answers
+  template <class L> void delta_slabs(std::vector<uint64_t>& off, const std::vector<uint32_t>& idx, std::vector<DeltaOut>& out, bool oc_bits, L launch) {
+    const size_t nq = idx.size();
+    std::vector<DlRes> r(nq);
+    std::vector<uint8_t> buf;
     auto pass = [&]() {
       b_dl_out.ensure(off[nq] + 64);
       b_dl_off.ensure((nq + 1) * 8);
       lmbe::h2d(b_dl_off.p, off.data(), (nq + 1) * 8);
       lmbe::tic(profiling);
-      LM_LAUNCH(k_delta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), (const uint32_t*)b_dl_bits.as<uint32_t>(), b_dl_out.as<uint8_t>(),
-                (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>(), units);
-      lmbe::toc("k_delta", dl_times, profiling);
+      launch();
       dl_launches++;
       lmbe::d2h(r.data(), b_dl_res.p, nq * sizeof(DlRes));
       lmbe::sync();
@@ -1991,10 +2012,82 @@ struct Engine {
       DeltaOut& o = out[idx[j]];
       o.status = r[j].status;
       if (r[j].status != ST_OK) continue;
-      o.other_changed = r[j].other_changed ? 1u : 0u;
+      o.other_changed = oc_bits ? r[j].other_changed : (r[j].other_changed ? 1u : 0u);
       o.json.assign(buf.begin() + poff[j], buf.begin() + poff[j] + r[j].len);
       if (r[j].cnt >= 2 && !order_members(o.json.data(), o.json.size(), r[j].cnt)) { o.status = ST_INTERNAL; o.json.clear(); }
     }
+  }
+
+  // ---- lm_delta_map (lm_k_delta_map.h): the Map deltas from a version A to the version the last run rendered.  A and V reach the
+  // device as lm_delta's do (delta_bounds); per query the device gets three 64-bit words per slot of the document's LWW table (winner at
+  // V, winner at A, key prefix) and a sort list of half as many entries, all cleared here.  k_mdelta_mark raises the winners from the op
+  // rows, k_mdelta checks the winner at V against the table the run left, classifies, sorts and renders into optimistic slabs (half the
+  // document's JSON + a few KB: the Maps' whole content from the empty version takes the second launch); the
+  // second launch, the packing and lm_delta_bytes are lm_delta's (delta_slabs).  LM_DELTA_SKEW=1 (tests of the self-check only) hands
+  // the device an EMPTY V: no row competes, every claimed slot's winner differs from the table's and every query on a document with a
+  // Map write must come back LM_UNSUPPORTED.  A document decoded without op rows (h_fused) cannot be answered here: the context runs
+  // its part once more through the row tables first (no_map_fused).
+  void delta_map(const std::vector<DeltaIn>& in, std::vector<DeltaOut>& out) {
+    lmbe::bind(sc);
+    if (!ran) throw std::runtime_error("lm_delta_map before lm_run");
+    if (shared_mode != 0) throw std::runtime_error("lm_delta_map: a folded batch has to be unfolded first");
+    out.assign(in.size(), DeltaOut());
+    dl_times.clear();
+    dl_launches = 0;
+    dl_d2h_bytes = 0;
+    std::map<uint32_t, DeltaDoc> info;
+    std::vector<uint32_t> idx, bnd;
+    std::vector<DlQuery> qs;
+    std::vector<uint64_t> off(1, 0);
+    uint64_t words = 0;
+    uint32_t blocks = 0;
+    const bool skew = getenv("LM_DELTA_SKEW") != nullptr;
+    std::vector<uint8_t> buf;
+    for (size_t k = 0; k < in.size(); k++) {
+      const uint32_t doc = in[k].doc;
+      DeltaOut& o = out[k];
+      std::vector<uint32_t> a;
+      const DeltaDoc* dip = nullptr;
+      if (!delta_bounds(in[k], "lm_delta_map", info, buf, o, a, dip)) continue;
+      const DocMeta& m = h_doc[doc];
+      if (doc < h_fused.size() && h_fused[doc]) throw std::runtime_error("lm_delta_map: a document decoded without op rows was not run again");
+      if (!skew && a == dip->V) { o.json = {'{', '}'}; continue; }   // A == V
+      DlQuery q;
+      memset(&q, 0, sizeof q);
+      q.doc = doc; q.n_bnd = m.n_peers; q.bnd0 = bnd.size();
+      bnd.insert(bnd.end(), a.begin(), a.end());
+      if (skew) bnd.insert(bnd.end(), m.n_peers, 0u); else bnd.insert(bnd.end(), dip->V.begin(), dip->V.end());
+      const uint32_t cap = doc < h_ht_cap.size() ? h_ht_cap[doc] : 0u;
+      q.n_words = cap; q.n_bits = cap / 2;
+      q.bits0 = words;
+      words += 3ull * cap + cap / 4 + 1;
+      q.row_blk0 = blocks;
+      blocks += cdiv(m.n_op, 64);
+      const uint64_t slab = m.out_len / 2 + 64ull * m.n_cont + 1024;   // (optimistic: a subscriber rarely lacks more than half the document)
+      off.push_back(off.back() + ((slab + 15) & ~15ull));
+      qs.push_back(q);
+      idx.push_back((uint32_t)k);
+    }
+    if (qs.empty()) return;
+    const size_t nq = qs.size();
+    bnd.push_back(0);
+    b_dl_q.ensure(nq * sizeof(DlQuery)); b_dl_bnd.ensure(bnd.size() * 4); b_dl_bits.ensure((words + 1) * 8); b_dl_res.ensure(nq * sizeof(DlRes));
+    lmbe::h2d(b_dl_q.p, qs.data(), nq * sizeof(DlQuery));
+    lmbe::h2d(b_dl_bnd.p, bnd.data(), bnd.size() * 4);
+    lmbe::dmemset(b_dl_bits.p, 0, (words + 1) * 8);
+    lmbe::dmemset(b_dl_res.p, 0, nq * sizeof(DlRes));
+    Dev d = last_d;
+    lmbe::reset_times();
+    if (blocks) {
+      lmbe::tic(profiling);
+      LM_LAUNCH(k_mdelta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (uint32_t)nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<unsigned long long>(), b_dl_res.as<DlRes>(),
+                (kn.lww_lds && !resident) ? 1u : 0u);
+      lmbe::toc("k_mdelta_mark", dl_times, profiling);
+    }
+    delta_slabs(off, idx, out, true, [&]() {
+      LM_LAUNCH(k_mdelta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), b_dl_bits.as<unsigned long long>(), b_dl_out.as<uint8_t>(), (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>());
+      lmbe::toc("k_mdelta", dl_times, profiling);
+    });
   }
 
   // ---- lm_export: the updates document `i` holds beyond `from_vv` (lm_export.h).  The blobs come back from the arena, the
