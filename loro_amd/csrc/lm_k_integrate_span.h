@@ -1679,6 +1679,10 @@ LM_DEV void integrate_span_body(Dev d, DevDag g, uint32_t dir_cap, uint32_t pmax
         // a MovableList move keeps the id of the item it deleted in its element slot (cp[]): the stored tracker is only usable
         // while the element layout is the one it was written under
         if (ML && ok && tk_ebase(tk, tk_pcap)[q] != d.elem_base[m.praw0 + lo]) lost = true;
+        // … and while the peer indices are: that id is a (peer index, counter) pair, which the renumbering of the leaves below does
+        // not reach — a retreat of the move would take its delete back from another peer's item (a new peer that sorts in front of
+        // the stored ones; found by tests/test_merge_ref_steps.py, "movable list")
+        if (ML && ok && lo != q) lost = true;
       }
       if (ML && (lmw::first(tk[4]) != m.elem0_lo || lmw::first(tk[5]) != m.elem0_hi)) lost = true;   // (the document's element slice moved)
       fresh = lmw::any(lost);

@@ -68,7 +68,26 @@ counted once here) — duplicate only blobs that apply; the applied end of a pee
 
 Map outcomes (`Model.map_outcomes`): what the LWW rule had to decide in this history, counted from the entries and the closures alone.
 
-NOT modelled: Tree, Counter, damaged input, snapshot state sections.
+Documents that arrive in steps (`Session`; loro.rs:568-649 import on an attached document, loro.rs:1625-1760 checkout, diff_calc.rs:299,
+state.rs:621-849).  A session holds the writers' changes of the whole history; `step(delivered_now, frontiers)` delivers some more of
+them and renders.  After a step the applied set is `Model(changes, delivered=everything delivered so far)`: pending changes carry over
+and resolve when their dependencies arrive — the model is rebuilt at every step, it is the definition and no fast path.  Every step
+STANDS AT two versions in order: the latest version after its import, then the checked-out one if it has one (an import into a
+checked-out document first returns to the latest version).  A container state, once created, stays (state.rs:621-849 never drops one):
+a root Text / List is shown from the first stood-at version on in which something in it is visible (a step that brings an insert
+together with its delete never shows it, a later step that empties it does not hide it again); a root Map is shown once an applied change
+holds an op for it, a root MovableList likewise, at every version.  `Model.value(frontiers, shown=…)` takes the sticky set; without it
+the rule of "Root containers" above (ONE import of everything, one checkout) holds.  Scope as above: no damaged input, no pending
+change delivered twice, and a step never fails — every checkout version lies inside the applied set of its step.
+A document that starts from a snapshot's STATE is the same session: it stands at the base version first and then takes the updates
+(`Session.step` with the base's changes, then with the rest).  Only the expected values are the model's; the state section's bytes are
+still written by the oracle's state writer (`_oracle.state_entries`).
+
+Cross-step outcomes (`Model(…, step_of=…)`, `Model.cross`): OUTCOMES counted only where the rule compared two elements delivered in
+DIFFERENT steps — "inserts": one of the atom's origins, "between": one of the elements between them, every other kind: the sibling
+the rule looked at.
+
+NOT modelled: Tree, Counter, damaged input, the BYTES of a snapshot's state section (a Python state writer; expected values are modelled).
 """
 from _values import to_json
 from loro_amd import wire
@@ -148,8 +167,13 @@ def _cmp_pos(a, b):
     return 0
 
 
-def _place(els, P, pos, id, what, stats):
-    """insert one element at visible position `pos` of version P"""
+def _place(els, P, pos, id, what, stats, step_of=None, cross=None):
+    """insert one element at visible position `pos` of version P.  `step_of` / `cross`: id -> delivery step, and the counts of the
+    decisions that compared two elements of different steps"""
+    def hit(kind, others):
+        stats[kind] += 1
+        if step_of is not None and any(o is not None and step_of[o] != step_of[id] for o in others):
+            cross[kind] += 1
     left_at = -1
     if pos > 0:
         left_at = _nth_visible(els, P, pos - 1)
@@ -160,37 +184,37 @@ def _place(els, P, pos, id, what, stats):
         right_at += 1
     origin_right = els[right_at].id if right_at < len(els) else None
     between = range(left_at + 1, right_at)
-    stats["inserts"] += 1
+    hit("inserts", (origin_left, origin_right))
     insert_at = left_at + 1
     if len(between):
-        stats["between"] += 1
+        hit("between", [els[i].id for i in between])
         mine = _parent_right(els, origin_left, origin_right)
         scanning, visited = False, set()
         for i in between:
             o = els[i]
             if o.origin_left != origin_left and (o.origin_left is None or o.origin_left not in visited):
-                stats["foreign_left_break"] += 1
+                hit("foreign_left_break", (o.id,))
                 break
             visited.add(o.id)
             if o.origin_left == origin_left:
                 if o.origin_right == origin_right:
                     if o.id[0] > id[0]:
-                        stats["same_right_break"] += 1
+                        hit("same_right_break", (o.id,))
                         break
-                    stats["same_right_pass"] += 1
+                    hit("same_right_pass", (o.id,))
                     scanning = False
                 else:
                     c = _cmp_pos(_parent_right(els, origin_left, o.origin_right), mine)
                     if c < 0:
-                        stats["diff_right_less"] += 1
+                        hit("diff_right_less", (o.id,))
                         scanning = True
                     elif c == 0:
-                        stats["diff_right_equal"] += 1
+                        hit("diff_right_equal", (o.id,))
                         if o.id[0] > id[0]:
                             break
                         scanning = False
                     else:
-                        stats["diff_right_greater"] += 1
+                        hit("diff_right_greater", (o.id,))
                         scanning = False
             if not scanning:
                 insert_at = i + 1
@@ -229,9 +253,12 @@ def _cut(ch, end):
 
 
 class Model:
-    def __init__(self, changes, delivered=None):
-        """`changes`: the writers' changes.  `delivered`: the changes the document's blobs hold, when they are not all of them"""
+    def __init__(self, changes, delivered=None, step_of=None):
+        """`changes`: the writers' changes.  `delivered`: the changes the document's blobs hold, when they are not all of them.
+        `step_of`: id -> the step that delivered it (a session): `cross` counts the sibling decisions between different steps"""
         self.pending = 0
+        self.step_of = step_of
+        self.cross = {k: 0 for k in OUTCOMES}
         if delivered is not None:
             delivered = list(delivered)
             end = applied_ends(delivered)
@@ -293,16 +320,16 @@ class Model:
                 self._apply_movable(ch, op, P, lam, els)
             elif op.kind == "text_insert":
                 for i, c in enumerate(op.text):
-                    _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("char", c), self.stats)
+                    _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("char", c), self.stats, self.step_of, self.cross)
             elif op.kind == "list_insert":
                 for i, v in enumerate(op.values):
-                    _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("value", v), self.stats)
+                    _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("value", v), self.stats, self.step_of, self.cross)
             elif op.kind == "style_start":
-                _place(els, P, op.pos, (ch.peer, op.counter), ("start", op), self.stats)
+                _place(els, P, op.pos, (ch.peer, op.counter), ("start", op), self.stats, self.step_of, self.cross)
             elif op.kind == "style_end":
                 start = next(e.what[1] for e in els if e.id == (ch.peer, op.counter - 1))
                 n_visible = sum(1 for e in els if _visible(e, P))
-                _place(els, P, min(start.pos + start.mark_len + 1, n_visible), (ch.peer, op.counter), ("end",), self.stats)
+                _place(els, P, min(start.pos + start.mark_len + 1, n_visible), (ch.peer, op.counter), ("end",), self.stats, self.step_of, self.cross)
             elif op.kind == "delete":
                 n = abs(op.signed_len)
                 first = wire._del_start(op)
@@ -322,14 +349,14 @@ class Model:
             for i, v in enumerate(op.values):
                 assert (ch.peer, lam + i) not in elems
                 elems[(ch.peer, lam + i)] = Element((lam + i, ch.peer, (ch.peer, op.counter + i), v))
-                _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("item", (ch.peer, lam + i)), self.stats)
+                _place(els, P | {(ch.peer, op.counter + k) for k in range(i)}, op.pos + i, (ch.peer, op.counter + i), ("item", (ch.peer, lam + i)), self.stats, self.step_of, self.cross)
         elif op.kind == "list_move":
             at = _nth_visible(els, P, op.move_from)
             assert at >= 0, ("move from beyond the visible length", id)
             assert els[at].what == ("item", op.elem), ("the move does not take the element its writer meant", id, op.elem, els[at].what)
             els[at].deleters.append(id)
             elems[op.elem].moves.append((lam, ch.peer, id))
-            _place(els, P | {id}, op.pos, id, ("item", op.elem), self.stats)
+            _place(els, P | {id}, op.pos, id, ("item", op.elem), self.stats, self.step_of, self.cross)
         elif op.kind == "list_set":
             assert elems[op.elem].insert[2] in P, ("a set of an element its writer has not seen", id)
             elems[op.elem].sets.append((lam, ch.peer, id, op.value))
@@ -449,21 +476,29 @@ class Model:
             return self._value(wire.CID(False, v.kind, "", id[0], id[1]), V)
         return v
 
-    def value(self, frontiers=None):
-        """the deep value: root name -> plain Python value"""
+    def seen_roots(self, frontiers=None):
+        """the root Text / List containers in which something is visible at the version"""
         V = self.version(frontiers)
+        return {cid for cid, els in self.seqs.items() if cid.root and cid.kind != wire.KIND_MOVABLE and any(_visible(e, V) for e in els)}
+
+    def value(self, frontiers=None, shown=None):
+        """the deep value: root name -> plain Python value.  `shown`: the root Text / List containers whose state exists (a session's
+        sticky set); None = one import of everything, then the checkout"""
+        V = self.version(frontiers)
+        if shown is None:
+            shown = self.seen_roots() | self.seen_roots(frontiers)
         roots = {}
         for cid in list(self.seqs) + list(self.maps):
             if not cid.root:
                 continue
-            if cid.kind not in (wire.KIND_MAP, wire.KIND_MOVABLE) and not (self.visible_ids(cid) or any(_visible(e, V) for e in self.seqs[cid])):
+            if cid.kind not in (wire.KIND_MAP, wire.KIND_MOVABLE) and cid not in shown:
                 continue
             assert cid.name not in roots, "two root containers share a name"
             roots[cid.name] = self._value(cid, V)
         return roots
 
-    def json(self, frontiers=None):
-        return to_json(self.value(frontiers)).encode("utf-8")
+    def json(self, frontiers=None, shown=None):
+        return to_json(self.value(frontiers, shown)).encode("utf-8")
 
     def vv(self, frontiers=None):
         out = {}
@@ -471,9 +506,34 @@ class Model:
             out[p] = max(out.get(p, 0), c + 1)
         return wire.encode_vv(out)
 
-    def result(self, frontiers=None):
+    def result(self, frontiers=None, shown=None):
         """(status, json, vv, pending) as merge_batch returns it"""
-        return (0, self.json(frontiers), self.vv(frontiers), self.pending)
+        return (0, self.json(frontiers, shown), self.vv(frontiers), self.pending)
+
+
+class Session:
+    """a document delivered in steps (module docstring, "Documents that arrive in steps")"""
+
+    def __init__(self, changes):
+        self.changes = list(changes)
+        self.delivered = []          # every change delivered so far, in the order of delivery
+        self.step_of = {}            # id -> the step that delivered it first
+        self.shown = set()           # root Text / List containers whose state exists
+        self.n_steps = 0
+        self.model = None            # the model of the applied set after the last step
+
+    def step(self, delivered_now, frontiers=None):
+        """deliver `delivered_now` (changes), stand at the latest version, then at `frontiers` if given -> (status, json, vv, pending)"""
+        for c in delivered_now:
+            self.delivered.append(c)
+            for k in range(c.counter, c.ctr_end):
+                self.step_of.setdefault((c.peer, k), self.n_steps)
+        self.n_steps += 1
+        m = self.model = Model(self.changes, delivered=self.delivered, step_of=self.step_of)
+        self.shown |= m.seen_roots()
+        if frontiers is not None:
+            self.shown |= m.seen_roots(frontiers)
+        return m.result(frontiers, self.shown)
 
 
 _GONE = object()
