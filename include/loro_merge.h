@@ -439,6 +439,47 @@ uint64_t lm_delta_bytes(lm_ctx* ctx);
  * lm_delta_map / lm_stage / lm_destroy.  The call changes nothing a run wrote. */
 int lm_delta_map(lm_ctx* ctx, const lm_delta_query* queries, size_t n, lm_delta_result* out);
 
+/* ---- MovableList deltas from a version to the rendered one: what LoroDoc::diff(a, b) and the ListDiffItem events of subscribe tell a
+ * subscriber about the MovableList containers (movable_list_state.rs:1136-1183, event.rs:244-250), answered on the device from the
+ * trackers, the table of move / set maxima and the op rows of the last lm_run (k_mldelta_mark, k_mldelta:
+ * loro_amd/csrc/lm_k_delta_movable.h).  Same query and result structs as lm_delta, no `units`; valid in the same states, the same -1
+ * for a call that cannot be answered (before lm_run among them), the same batch shapes.  A = from_vv, V = the version that run
+ * rendered (the latest version, the entry's checkout, a resident document's state); A is contained in V as id sets.
+ *
+ * Definition, for one MovableList container.
+ *   - Items.  Every atom of an insert op and every move op is an ITEM whose id is that op's id; el(i) is the element it positions (an
+ *     element is what an insert atom created).  The items stand in the tracker's sequence order, which does not depend on the version.
+ *   - Position.  pos_X(e) = the greatest, by (lamport, peer id), of e's insert and its moves whose ids lie in X.
+ *   - Value.  val_X(e) = the greatest, by the same order, of e's insert and its sets in X.
+ *   - Item i SHOWS at X iff id(i) is in X, i is pos_X(el(i)), and no delete atom whose own id lies in X targets i.  (A move also
+ *     removes the item it took the element from; the winner of X is never such an item, so nothing more is needed.)
+ *   - Value unchanged for e between A and V: val_A(e) and val_V(e) are the same op, or different ops whose values are equal under
+ *     LoroValue equality as lm_delta_map compares them.  A pair that comparison does not decide (two nested List values, two nested
+ *     Map values) counts as CHANGED and sets bit 1 of other_changed: the delta stays correct, it is only less minimal.
+ *   - Classes per item.  K: shows at A and at V, value unchanged.  R: shows at both, value changed — one delete and one insert in
+ *     place.  I: shows at V only.  D: shows at A only.
+ *   - from_move.  An I carries "from_move" iff its element shows at A (necessarily at another item, which is then a D) and its value
+ *     is unchanged: "moved from a deletion in the same delta and the value is not changed".
+ * Canonical form (lm_delta's): a maximal K run gives {"retain":n}; within a gap all inserts come first, in sequence order, consecutive
+ * inserts with the same flag in one op — {"insert":[v,...]} or {"insert":[v,...],"from_move":true} — then one {"delete":n}; a trailing
+ * retain is dropped; a container with an empty delta is left out; containers in the bytewise order of their JSON-encoded keys; values
+ * in lm_fetch's canonical form; a child container is the parrot string (U+1F99C ':' ContainerID Display) of the ContainerID of the op
+ * that wrote it (the winning set, else the insert).  Result bytes of a query:
+ *   {"cid:root-ml:MovableList":[{"delete":1},{"retain":2},{"insert":["a"],"from_move":true}],...}        {} when nothing changed.
+ * other_changed of this call: bit 0 — an op with an id in V \ A went to a Tree or Counter container; bit 1 — an undecided nested pair
+ * was treated as changed.  Text, List and Map ops set nothing (lm_delta and lm_delta_map cover them).
+ * A document that holds Tree or Counter ops is one lm_fetch reports as LM_UNSUPPORTED together with its JSON; that status is the
+ * rendering's, not this call's: the query comes back LM_OK with the MovableList deltas, and bit 0 tells the host that the part of the
+ * document the device does not render changed as well.
+ * Statuses: lm_delta's (LM_DECODE_ERROR: from_vv is no version vector; LM_FRONTIERS_NOT_FOUND: A is not contained in V).
+ * LM_UNSUPPORTED also when the kernel's self-check failed — for every item "visible by the tracker's status word" must equal "id in V
+ * and not removed by a delete or move in V", and for every element the move and set winners at V found from the op rows must be the
+ * ops the run left in the document's table — or when a slot lies beyond the call's bitmaps or tables.  A = V, an LWW Map document
+ * decoded without op rows, and a document that holds neither a MovableList nor an applied Tree / Counter op are answered {} on the host.
+ * lm_delta_bytes reports the bytes of whichever of lm_delta / lm_delta_map / lm_delta_movable ran last; `json` is valid until the next
+ * of these calls / lm_stage / lm_destroy.  The call changes nothing a run wrote: lm_fetch gives the same bytes afterwards. */
+int lm_delta_movable(lm_ctx* ctx, const lm_delta_query* queries, size_t n, lm_delta_result* out);
+
 /* Wave-primitive self test on the device (DPP scan, ballot ranks); returns the number of mismatches. */
 int lm_selftest(lm_ctx* ctx);
 

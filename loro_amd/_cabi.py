@@ -50,7 +50,7 @@ CURSOR_OK, CURSOR_DELETED, CURSOR_ID_NOT_FOUND, CURSOR_CONTAINER_NOT_FOUND, CURS
 SYMBOLS = ["create", "destroy", "last_error", "merge_batch", "stage", "run", "fetch", "get_stats", "set_profiling", "kernel_time", "selftest", "result_meta", "result_hashes", "n_streams", "run_async", "wait",
            "encode_block", "encode_updates", "free_bytes", "import", "resident_fresh", "import_modes", "import_lca", "export", "comm_unique_id", "comm_init", "summary_allgather",
            "summary_layout", "summary_rows_device", "summary_allgather_device", "shared_documents", "richtext", "richtext_result", "fused_documents", "redo_documents", "state_documents", "host_alloc", "host_free", "staged_direct",
-           "cursor_pos", "cursor_at", "delta", "delta_bytes", "delta_map"]
+           "cursor_pos", "cursor_at", "delta", "delta_bytes", "delta_map", "delta_movable"]
 
 
 class Binding:
@@ -95,6 +95,8 @@ class Binding:
         self.delta.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeltaQuery), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(DeltaResult)]
         self.delta_map = g("delta_map"); self.delta_map.restype = ctypes.c_int
         self.delta_map.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeltaQuery), ctypes.c_size_t, ctypes.POINTER(DeltaResult)]
+        self.delta_movable = g("delta_movable"); self.delta_movable.restype = ctypes.c_int
+        self.delta_movable.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeltaQuery), ctypes.c_size_t, ctypes.POINTER(DeltaResult)]
         self.delta_bytes = g("delta_bytes"); self.delta_bytes.restype = ctypes.c_uint64; self.delta_bytes.argtypes = [ctypes.c_void_p]
         self.comm_unique_id = g("comm_unique_id"); self.comm_unique_id.restype = ctypes.c_int; self.comm_unique_id.argtypes = [ctypes.c_char_p]
         self.comm_init = g("comm_init"); self.comm_init.restype = ctypes.c_int; self.comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
@@ -337,6 +339,21 @@ class Context:
             keep.append(vv)
             qs[k].doc = doc; qs[k].from_vv = vv; qs[k].from_vv_len = len(vv) if vv else 0
         if self.b.delta_map(self.h, qs, n, out) != 0:
+            raise RuntimeError(self.b.last_error(self.h).decode())
+        return [(out[k].status, out[k].other_changed, ctypes.string_at(out[k].json, out[k].json_len) if out[k].json_len else b"") for k in range(n)]
+
+    def delta_movable(self, queries):
+        """lm_delta_movable (LoroDoc::diff / the ListDiffItem events of a MovableList): the MovableList deltas from a version to the
+        version the last run rendered — retain / insert (with from_move) / delete.  queries: [(doc, from_vv)] as for delta().  Returns
+        [(status, other_changed, json bytes)] — other_changed bit 0: a Tree / Counter received an op in V \\ A, bit 1: two nested List /
+        Map values the device does not compare were treated as changed.  self.b.delta_bytes(self.h) = the bytes the call copied back."""
+        n = len(queries)
+        qs, out, keep = (DeltaQuery * max(n, 1))(), (DeltaResult * max(n, 1))(), []
+        for k, (doc, vv) in enumerate(queries):
+            vv = None if vv is None else bytes(vv)
+            keep.append(vv)
+            qs[k].doc = doc; qs[k].from_vv = vv; qs[k].from_vv_len = len(vv) if vv else 0
+        if self.b.delta_movable(self.h, qs, n, out) != 0:
             raise RuntimeError(self.b.last_error(self.h).decode())
         return [(out[k].status, out[k].other_changed, ctypes.string_at(out[k].json, out[k].json_len) if out[k].json_len else b"") for k in range(n)]
 

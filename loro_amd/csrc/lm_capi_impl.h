@@ -585,6 +585,8 @@ struct lm_ctx_impl {
     if (any) { run(); sum_host_rows(); }
     delta_route(nullptr, in, out, [&](lm::Engine& e, const std::vector<lm::Engine::DeltaIn>& sub, std::vector<lm::Engine::DeltaOut>& r) { e.delta_map(sub, r); });
   }
+  // ---- lm_delta_movable (lm_k_delta_movable.h): routed like lm_delta
+  void delta_movable(std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& out) { delta_route("lm_delta_movable", in, out, [&](lm::Engine& e, const std::vector<lm::Engine::DeltaIn>& sub, std::vector<lm::Engine::DeltaOut>& r) { e.delta_movable(sub, r); }); }
   // `prepare`: the call's name for cursor_prepare, nullptr when the caller has done that
   template <class F> void delta_route(const char* prepare, std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& out, F call) {
     if (prepare) cursor_prepare(prepare);
@@ -976,17 +978,17 @@ int LM_API(cursor_at)(void* c, const lm_cursor_at_query_c* qs, size_t n, lm_curs
 // the last lm_run (lm_k_delta.h)
 typedef struct lm_delta_query_c { size_t doc; const uint8_t* from_vv; size_t from_vv_len; } lm_delta_query_c;
 typedef struct lm_delta_result_c { int32_t status; uint32_t other_changed; const uint8_t* json; size_t json_len; } lm_delta_result_c;
-int LM_API(delta)(void* c, const lm_delta_query_c* qs, size_t n, int units, lm_delta_result_c* out) {
-  auto* x = (lm_ctx_impl*)c;
+// what the three delta calls share: the queries checked and handed to `call(in, r)`, the answers' bytes kept in the context
+extern "C++" {
+template <class F> static int delta_entry(lm_ctx_impl* x, const char* who, const lm_delta_query_c* qs, size_t n, lm_delta_result_c* out, F call) {
   try {
-    if (units < 0 || units > 1) throw std::runtime_error("lm_delta: units is 0 (Unicode scalars) or 1 (UTF-16 code units)");
     std::vector<lm::Engine::DeltaIn> in(n);
     for (size_t k = 0; k < n; k++) {
-      if (qs[k].doc >= x->api_docs()) throw std::runtime_error("lm_delta: no such document");
+      if (qs[k].doc >= x->api_docs()) throw std::runtime_error(std::string(who) + ": no such document");
       in[k].doc = (uint32_t)qs[k].doc; in[k].vv = qs[k].from_vv; in[k].vv_len = qs[k].from_vv ? qs[k].from_vv_len : 0;
     }
     std::vector<lm::Engine::DeltaOut> r;
-    x->delta(in, units, r);
+    call(in, r);
     x->dl_json.resize(n);
     for (size_t k = 0; k < n; k++) {
       x->dl_json[k].swap(r[k].json);
@@ -997,27 +999,23 @@ int LM_API(delta)(void* c, const lm_delta_query_c* qs, size_t n, int units, lm_d
     return 0;
   } catch (const std::exception& e) { x->err = e.what(); return -1; }
 }
+}  // extern "C++"
+int LM_API(delta)(void* c, const lm_delta_query_c* qs, size_t n, int units, lm_delta_result_c* out) {
+  auto* x = (lm_ctx_impl*)c;
+  if (units < 0 || units > 1) { x->err = "lm_delta: units is 0 (Unicode scalars) or 1 (UTF-16 code units)"; return -1; }
+  return delta_entry(x, "lm_delta", qs, n, out, [&](std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& r) { x->delta(in, units, r); });
+}
 // ---- Map deltas from a version to the rendered one (include/loro_merge.h): on the device, from the LWW tables and op rows of the
 // last lm_run (lm_k_delta_map.h)
 int LM_API(delta_map)(void* c, const lm_delta_query_c* qs, size_t n, lm_delta_result_c* out) {
   auto* x = (lm_ctx_impl*)c;
-  try {
-    std::vector<lm::Engine::DeltaIn> in(n);
-    for (size_t k = 0; k < n; k++) {
-      if (qs[k].doc >= x->api_docs()) throw std::runtime_error("lm_delta_map: no such document");
-      in[k].doc = (uint32_t)qs[k].doc; in[k].vv = qs[k].from_vv; in[k].vv_len = qs[k].from_vv ? qs[k].from_vv_len : 0;
-    }
-    std::vector<lm::Engine::DeltaOut> r;
-    x->delta_map(in, r);
-    x->dl_json.resize(n);
-    for (size_t k = 0; k < n; k++) {
-      x->dl_json[k].swap(r[k].json);
-      x->dl_json[k].push_back(0);   // (never an empty vector: json is a valid pointer for every query)
-      out[k].status = r[k].status; out[k].other_changed = r[k].other_changed;
-      out[k].json = x->dl_json[k].data(); out[k].json_len = x->dl_json[k].size() - 1;
-    }
-    return 0;
-  } catch (const std::exception& e) { x->err = e.what(); return -1; }
+  return delta_entry(x, "lm_delta_map", qs, n, out, [&](std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& r) { x->delta_map(in, r); });
+}
+// ---- MovableList deltas from a version to the rendered one (include/loro_merge.h): on the device, from the trackers, the table of
+// move / set maxima and the op rows of the last lm_run (lm_k_delta_movable.h)
+int LM_API(delta_movable)(void* c, const lm_delta_query_c* qs, size_t n, lm_delta_result_c* out) {
+  auto* x = (lm_ctx_impl*)c;
+  return delta_entry(x, "lm_delta_movable", qs, n, out, [&](std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& r) { x->delta_movable(in, r); });
 }
 uint64_t LM_API(delta_bytes)(void* c) { return ((lm_ctx_impl*)c)->dl_d2h_bytes; }
 int LM_API(get_stats)(void* c, lm_run_stats_c* s) {

@@ -27,6 +27,7 @@
 #include "lm_k_cursor.h"
 #include "lm_k_delta.h"
 #include "lm_k_delta_map.h"
+#include "lm_k_delta_movable.h"
 #include "lm_snapshot.h"
 #include "lm_export.h"
 #include "lm_snapshot_base.h"
@@ -2087,6 +2088,80 @@ struct Engine {
     delta_slabs(off, idx, out, true, [&]() {
       LM_LAUNCH(k_mdelta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), b_dl_bits.as<unsigned long long>(), b_dl_out.as<uint8_t>(), (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>());
       lmbe::toc("k_mdelta", dl_times, profiling);
+    });
+  }
+
+  // ---- lm_delta_movable (lm_k_delta_movable.h): the MovableList deltas from a version A to the version the last run rendered.  A and V
+  // reach the device as lm_delta's do (delta_bounds); per query the device gets two 64-bit winner words per slot of the document's
+  // table (at V, at A) and two bitmaps over the document's element slots (gone at A, gone at V), all cleared here.  k_mldelta_mark fills
+  // them from the op rows, k_mldelta checks them against the status words and the table the run left, classifies and renders into
+  // optimistic slabs (twice the document's JSON + a few KB); the second launch, the packing and lm_delta_bytes are lm_delta's (delta_slabs).
+  // LM_DELTA_SKEW=1 (tests of the self-check only) hands the device a V that is one counter short for every peer, as in delta().  An LWW
+  // Map document decoded without op rows holds no MovableList: answered here, as is a document with neither DF_MOVABLE nor DF_SOFT_UNSUPPORTED.
+  void delta_movable(const std::vector<DeltaIn>& in, std::vector<DeltaOut>& out) {
+    lmbe::bind(sc);
+    if (!ran) throw std::runtime_error("lm_delta_movable before lm_run");
+    if (shared_mode != 0) throw std::runtime_error("lm_delta_movable: a folded batch has to be unfolded first");
+    out.assign(in.size(), DeltaOut());
+    dl_times.clear();
+    dl_launches = 0;
+    dl_d2h_bytes = 0;
+    std::map<uint32_t, DeltaDoc> info;
+    std::vector<uint32_t> idx, bnd;
+    std::vector<DlQuery> qs;
+    std::vector<uint64_t> off(1, 0);
+    uint64_t words = 0;
+    uint32_t blocks = 0;
+    const bool skew = getenv("LM_DELTA_SKEW") != nullptr;
+    std::vector<uint8_t> buf;
+    for (size_t k = 0; k < in.size(); k++) {
+      const uint32_t doc = in[k].doc;
+      DeltaOut& o = out[k];
+      std::vector<uint32_t> a;
+      const DeltaDoc* dip = nullptr;
+      if (!delta_bounds(in[k], "lm_delta_movable", info, buf, o, a, dip)) continue;
+      const DocMeta& m = h_doc[doc];
+      if ((doc < h_fused.size() && h_fused[doc]) || a == dip->V) { o.json = {'{', '}'}; continue; }   // Maps only; A == V
+      // no MovableList, and no applied Tree / Counter op that bit 0 could report (k_map_lww / k_map_lww_doc flag every one): nothing to launch
+      if (!(m.flags & (DF_MOVABLE | DF_SOFT_UNSUPPORTED))) { o.json = {'{', '}'}; continue; }
+      DlQuery q;
+      memset(&q, 0, sizeof q);
+      q.doc = doc; q.n_bnd = m.n_peers; q.bnd0 = bnd.size();
+      bnd.insert(bnd.end(), a.begin(), a.end());
+      bnd.insert(bnd.end(), dip->V.begin(), dip->V.end());
+      if (skew) for (uint32_t p = 0; p < m.n_peers; p++) if (bnd[bnd.size() - m.n_peers + p] > a[p]) bnd[bnd.size() - m.n_peers + p]--;
+      q.n_bits = m.atoms;
+      if (resident && doc < tk_elem_cap.size() && tk_elem_cap[doc] > q.n_bits) q.n_bits = tk_elem_cap[doc];
+      q.n_words = q.n_bits / 32 + 1;
+      q.pad = doc < h_ht_cap.size() ? h_ht_cap[doc] : 0u;
+      q.bits0 = words;
+      words += 2ull * q.pad + q.n_words;   // (two bitmaps of n_words 32-bit words)
+      q.row_blk0 = blocks;
+      blocks += cdiv(m.n_op, 64);
+      const uint64_t slab = 2ull * m.out_len + 64ull * m.n_cont + 1024;   // (lm_delta's: a delta of single-item ops is larger than the values it moves)
+      off.push_back(off.back() + ((slab + 15) & ~15ull));
+      qs.push_back(q);
+      idx.push_back((uint32_t)k);
+    }
+    if (qs.empty()) return;
+    const size_t nq = qs.size();
+    bnd.push_back(0);
+    b_dl_q.ensure(nq * sizeof(DlQuery)); b_dl_bnd.ensure(bnd.size() * 4); b_dl_bits.ensure((words + 1) * 8); b_dl_res.ensure(nq * sizeof(DlRes));
+    lmbe::h2d(b_dl_q.p, qs.data(), nq * sizeof(DlQuery));
+    lmbe::h2d(b_dl_bnd.p, bnd.data(), bnd.size() * 4);
+    lmbe::dmemset(b_dl_bits.p, 0, (words + 1) * 8);
+    lmbe::dmemset(b_dl_res.p, 0, nq * sizeof(DlRes));
+    Dev d = last_d;
+    lmbe::reset_times();
+    if (blocks) {
+      lmbe::tic(profiling);
+      LM_LAUNCH(k_mldelta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (uint32_t)nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<unsigned long long>(), b_dl_res.as<DlRes>());
+      lmbe::toc("k_mldelta_mark", dl_times, profiling);
+    }
+    delta_slabs(off, idx, out, true, [&]() {
+      LM_LAUNCH(k_mldelta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), (const unsigned long long*)b_dl_bits.as<unsigned long long>(), b_dl_out.as<uint8_t>(),
+                (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>());
+      lmbe::toc("k_mldelta", dl_times, profiling);
     });
   }
 
