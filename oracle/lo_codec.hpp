@@ -161,8 +161,15 @@ inline std::vector<uint8_t> take_bool_rle(Reader& r, size_t n) {
   std::vector<uint8_t> out;
   out.reserve(n);
   bool v = false;
+  int zeros = 0;
   while (out.size() < n) {
     uint64_t run = r.uleb();
+    // The grammar text names only the FIRST run as one that may be zero.  The kernels' reader (lm_dev_util.h bool_next) reads at most
+    // four run lengths for one value, i.e. it refuses a fourth zero-length run in a row; so does this one, with the same code —
+    // "the reference's value or a rejection", and never a difference between kernel and checker (NEXT.md; pinned by
+    // tests/test_column_forms.py::test_zero_length_bool_runs).
+    zeros = run == 0 ? zeros + 1 : 0;
+    if (zeros >= 4) fail(ST_DECODE_ERROR, "BoolRle: four zero-length runs in a row");
     if (out.size() + run > n) fail(ST_DECODE_ERROR, "BoolRle too many");
     out.insert(out.end(), (size_t)run, v ? 1 : 0);
     v = !v;
@@ -651,6 +658,9 @@ inline void decode_block(Reader blk, std::vector<Change>& out, RawBlock* raw = n
     col_len = decode_any_rle_uvar(ops_b.bytes());
     size_t n = col_container.size();
     if (col_prop.size() != n || col_vt.size() != n || col_len.size() != n) fail(ST_DECODE_ERROR, "op column length mismatch");
+    // `prop` is a DeltaRle<i32> column: the reference sums in i128 and fails the narrowing, and so do the kernels (a position of 2^35 was
+    // refused by them and wrapped here: tests/test_column_forms.py::test_documents_beyond_the_limits)
+    for (int64_t v : col_prop) if (v < INT32_MIN || v > INT32_MAX) fail(ST_DECODE_ERROR, "prop beyond i32");
   }
   // ---- delete start ids (outdated_encode_reordered.rs:480-489)
   std::vector<int64_t> del_peer, del_counter, del_len;
