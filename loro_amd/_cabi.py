@@ -312,50 +312,37 @@ class Context:
             raise RuntimeError(self.b.last_error(self.h).decode())
         return [(out[k].status, (out[k].peer, out[k].counter) if out[k].has_id else None, out[k].side, out[k].origin_pos) for k in range(n)]
 
-    def delta(self, queries, units=0):
-        """lm_delta (LoroDoc::diff / the TextDelta and ListDiffItem events): the Text / List deltas from a version to the version the
-        last run rendered.  queries: [(doc, from_vv)] — from_vv = VersionVector::encode bytes (what fetch() returned as `vv` at the
-        earlier step) or None for the empty version; units 0: Text counts in Unicode scalars, 1: in UTF-16 code units.
-        Returns [(status, other_changed, json bytes)].  self.b.delta_bytes(self.h) = the bytes the call copied back from the device."""
+    def _delta(self, call, queries, *units):
         n = len(queries)
         qs, out, keep = (DeltaQuery * max(n, 1))(), (DeltaResult * max(n, 1))(), []
         for k, (doc, vv) in enumerate(queries):
             vv = None if vv is None else bytes(vv)
             keep.append(vv)
             qs[k].doc = doc; qs[k].from_vv = vv; qs[k].from_vv_len = len(vv) if vv else 0
-        if self.b.delta(self.h, qs, n, units, out) != 0:
+        if call(self.h, qs, n, *units, out) != 0:
             raise RuntimeError(self.b.last_error(self.h).decode())
         return [(out[k].status, out[k].other_changed, ctypes.string_at(out[k].json, out[k].json_len) if out[k].json_len else b"") for k in range(n)]
+
+    def delta(self, queries, units=0):
+        """lm_delta (LoroDoc::diff / the TextDelta and ListDiffItem events): the Text / List deltas from a version to the version the
+        last run rendered.  queries: [(doc, from_vv)] — from_vv = VersionVector::encode bytes (what fetch() returned as `vv` at the
+        earlier step) or None for the empty version; units 0: Text counts in Unicode scalars, 1: in UTF-16 code units.
+        Returns [(status, other_changed, json bytes)].  self.b.delta_bytes(self.h) = the bytes the call copied back from the device."""
+        return self._delta(self.b.delta, queries, units)
 
     def delta_map(self, queries):
         """lm_delta_map (LoroDoc::diff / the MapDelta events): the Map deltas from a version to the version the last run rendered.
         queries: [(doc, from_vv)] as for delta().  Returns [(status, other_changed, json bytes)] — other_changed bit 0: a MovableList /
         Tree / Counter received an op in V \\ A, bit 1: a key whose two nested List / Map values the device does not compare was left
         out.  self.b.delta_bytes(self.h) = the bytes the call copied back from the device."""
-        n = len(queries)
-        qs, out, keep = (DeltaQuery * max(n, 1))(), (DeltaResult * max(n, 1))(), []
-        for k, (doc, vv) in enumerate(queries):
-            vv = None if vv is None else bytes(vv)
-            keep.append(vv)
-            qs[k].doc = doc; qs[k].from_vv = vv; qs[k].from_vv_len = len(vv) if vv else 0
-        if self.b.delta_map(self.h, qs, n, out) != 0:
-            raise RuntimeError(self.b.last_error(self.h).decode())
-        return [(out[k].status, out[k].other_changed, ctypes.string_at(out[k].json, out[k].json_len) if out[k].json_len else b"") for k in range(n)]
+        return self._delta(self.b.delta_map, queries)
 
     def delta_movable(self, queries):
         """lm_delta_movable (LoroDoc::diff / the ListDiffItem events of a MovableList): the MovableList deltas from a version to the
         version the last run rendered — retain / insert (with from_move) / delete.  queries: [(doc, from_vv)] as for delta().  Returns
         [(status, other_changed, json bytes)] — other_changed bit 0: a Tree / Counter received an op in V \\ A, bit 1: two nested List /
         Map values the device does not compare were treated as changed.  self.b.delta_bytes(self.h) = the bytes the call copied back."""
-        n = len(queries)
-        qs, out, keep = (DeltaQuery * max(n, 1))(), (DeltaResult * max(n, 1))(), []
-        for k, (doc, vv) in enumerate(queries):
-            vv = None if vv is None else bytes(vv)
-            keep.append(vv)
-            qs[k].doc = doc; qs[k].from_vv = vv; qs[k].from_vv_len = len(vv) if vv else 0
-        if self.b.delta_movable(self.h, qs, n, out) != 0:
-            raise RuntimeError(self.b.last_error(self.h).decode())
-        return [(out[k].status, out[k].other_changed, ctypes.string_at(out[k].json, out[k].json_len) if out[k].json_len else b"") for k in range(n)]
+        return self._delta(self.b.delta_movable, queries)
 
     def comm_init(self, rank=0, world=1, unique_id=None):
         if self.b.comm_init(self.h, rank, world, unique_id or bytes(128)) != 0:

@@ -10,21 +10,19 @@
 // over the op rows.  A key is reported iff its two winners are different ops and (one of them is absent or a delete while the other
 // is not, or both are sets whose values differ under LoroValue equality — diff_calc.rs:545-610, loro-common/src/value.rs:29-44).
 //
-// k_mdelta_mark lane = op row, k_delta_mark's grid (query x 64-row chunks, DlQuery.row_blk0): a Map write row with ctr < V[peer] finds
-//               its key's slot in the document's table — by the hash of the kernel that BUILT the table, restated below — and raises
-//               the query's winV[slot] (and winA[slot] when also ctr < A[peer]) by atomic_max64 of the builders' packed word, after a
-//               plain load (k_map_lww: a row that is already beaten needs no atomic).  A row whose key has no slot makes the query
+// k_mdelta_mark lane = op row (dl_mark_row): a Map write row with ctr < V[peer] finds its key's slot in the document's table — by the
+//               hash of the kernel that BUILT the table, restated below — and raises the query's winV[slot] (and winA[slot] when also
+//               ctr < A[peer]) to the builders' packed word (dl_win_word, dl_win_raise).  A row whose key has no slot makes the query
 //               LM_UNSUPPORTED.  Rows of MovableList / Tree / Counter containers with an id in V \ A set bit 0 of other_changed.
 // k_mdelta      one wave per query, lanes over the claimed slots 64 per step.  SELF-CHECK: winV[slot] == best[slot] for every claimed
 //               Map slot — the LWW builders against the op rows read again; a mismatch gives the query LM_UNSUPPORTED: the right
 //               value or a refusal, never a guess.  The changed slots are compacted into the query's own list, bitonic-sorted by
 //               (container, key bytes) and rendered container by container: {"updated":{…},"deleted":[…]}.  A pair of nested List
 //               values or of nested Map values from different ops is not decided: the key is left out, bit 1 of other_changed is set.
-//               Output goes into optimistic per-query slabs; the kernel never writes beyond a slab and always reports the exact size.
-// k_delta_pack  (lm_k_delta.h) moves the written bytes into one dense buffer.
+// The query and result rows, the slabs and k_delta_pack are lm_k_delta.h's.
 //
-// The query's words (DlQuery, as Engine::delta_map fills it): bits0 = first 64-bit word of the query's scratch, n_words = the slots of
-// the document's table (cap): winV[cap], winA[cap], key prefixes[cap], then the sort list of n_bits (= cap / 2) 32-bit entries.
+// The query's scratch (DlQuery: cap = the slots of the document's table, no bitmaps): winV[cap], winA[cap] (dl_win), then 64-bit key
+// prefixes[cap], then the sort list of cap / 2 32-bit entries.
 #pragma once
 #include "lm_k_delta.h"
 
@@ -66,88 +64,43 @@ LM_DEV uint32_t md_find(const Dev& d, const unsigned long long* keys, uint32_t c
   return NONE;
 }
 
-LM_KERNEL void k_mdelta_mark(Dev d, const DlQuery* qs, uint32_t nq, const uint32_t* bnd, unsigned long long* win, DlRes* res, uint32_t lds_on) {
-  const uint32_t b = (uint32_t)lmw::bid();
-  uint32_t lo = 0, hi = nq;   // (k_delta_mark: the last query whose first workgroup is at or in front of this one)
-  while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (qs[mid].row_blk0 <= b) lo = mid; else hi = mid; }
-  const DlQuery Q = qs[lo];
-  const DocMeta m = d.doc[Q.doc];
-  const uint32_t i = (b - Q.row_blk0) * 64 + (uint32_t)lmw::lane();
-  if (i >= m.n_op || status_fatal(m.status)) return;
-  const OpRow r = d.op[m.op0 + i];
-  const uint32_t kind = (r.cidx_kind >> 16) & 0xff, cidx = r.cidx_kind & 0xffff;
-  const ChangeRow ch = d.chg[r.chg];
-  if (cidx >= m.n_cont || ch.peer >= Q.n_bnd) return;
-  const uint32_t bA = bnd[Q.bnd0 + ch.peer], bV = bnd[Q.bnd0 + Q.n_bnd + ch.peer];
-  const uint32_t ck = d.cont[m.cid0 + cidx].kind_root & 0xff;
-  if (ck == CK_MOVABLE || ck == CK_TREE || ck == CK_COUNTER) {
-    if (r.ctr < bV && (uint64_t)r.ctr + (r.len ? r.len : 1u) > bA) lmw::atomic_or(&res[lo].other_changed, 1u);
+LM_KERNEL void k_mdelta_mark(Dev d, const DlQuery* qs, uint32_t nq, const uint32_t* bnd, uint32_t* scr, DlRes* res, uint32_t lds_on) {
+  DlRow x;
+  if (!dl_mark_row(d, qs, nq, bnd, x)) return;
+  const OpRow& r = x.r;
+  if (x.ck == CK_MOVABLE || x.ck == CK_TREE || x.ck == CK_COUNTER) {
+    if (dl_other_changed(r, x.bA, x.bV)) lmw::atomic_or(&res[x.q].other_changed, 1u);
     return;
   }
-  if (ck != CK_MAP || (kind != OK_MAP_SET && kind != OK_MAP_DEL)) return;
+  if (x.ck != CK_MAP || (x.kind != OK_MAP_SET && x.kind != OK_MAP_DEL)) return;
   if (!d.chg_flag[r.chg]) return;                              // not an applied change
-  if (r.ctr < ch.ctr + d.chg_skip[r.chg]) return;              // already-known prefix of a sliced change
-  if (r.ctr >= bV) return;                                     // beyond the rendered version: does not compete
-  const uint32_t cap = Q.n_words;
-  auto refuse = [&]() { (void)lmw::atomic_max32((uint32_t*)&res[lo].status, (uint32_t)ST_UNSUPPORTED); };
-  if (cap == 0 || cap != d.ht_cap[Q.doc] || i >= (1u << 24) || ch.peer >= 256u) { refuse(); return; }
-  const uint32_t slot = md_find(d, d.ht_key + d.ht0[Q.doc], cap, cidx, r.a0, md_doc_hash(lds_on, cap, m.flags));
-  if (slot == NONE) { refuse(); return; }
-  const unsigned long long v = (((unsigned long long)(d.chg_lamport[r.chg] + (r.ctr - ch.ctr)) << 32) | ((unsigned long long)ch.peer << 24) | i) + 1;
-  unsigned long long* wV = win + Q.bits0 + slot;
-  if (*wV < v) (void)lmw::atomic_max64(wV, v);
-  if (r.ctr < bA && wV[cap] < v) (void)lmw::atomic_max64(wV + cap, v);
+  if (r.ctr < x.ch.ctr + d.chg_skip[r.chg]) return;            // already-known prefix of a sliced change
+  if (r.ctr >= x.bV) return;                                   // beyond the rendered version: does not compete
+  const unsigned long long v = dl_win_word(d, x);
+  if (!v) { dl_refuse(res, x.q); return; }
+  const uint32_t slot = md_find(d, d.ht_key + d.ht0[x.Q.doc], x.Q.cap, x.cidx, r.a0, md_doc_hash(lds_on, x.Q.cap, x.m.flags));
+  if (slot == NONE) { dl_refuse(res, x.q); return; }
+  dl_win_raise(dl_win(scr, x.Q) + slot, x.Q.cap, v, r.ctr < x.bA);
 }
 
-// LoroValue equality of two plain values (loro-common/src/value.rs:29-44), one pair per lane.  0 = differ, 1 = equal, 2 = not decided
-// here (two nested List values or two nested Map values), 3 = the bytes do not parse
-LM_DEV uint32_t md_value_eq(const uint8_t* pa, const uint8_t* ea, const uint8_t* pb, const uint8_t* eb) {
-  if (pa >= ea || pb >= eb) return 3;
-  Rd a = rd_make(pa, (uint64_t)(ea - pa)), b = rd_make(pb, (uint64_t)(eb - pb));
-  const uint32_t ta = rd_u8(a), tb = rd_u8(b);
-  if (ta > 9 || tb > 9) return 3;
-  if (ta != tb) return 0;                         // another kind (I64 3 against F64 3.0), true against false
-  if (ta <= 2) return 1;
-  if (ta == 3) { const int64_t x = rd_sleb(a), y = rd_sleb(b); return (a.bad || b.bad) ? 3u : (x == y ? 1u : 0u); }
-  if (ta == 4) {                                  // a == b || (a.is_nan() && b.is_nan()): 0.0 equals -0.0
-    uint64_t x = 0, y = 0;
-    for (int k = 0; k < 8; k++) { x = (x << 8) | rd_u8(a); y = (y << 8) | rd_u8(b); }
-    if (a.bad || b.bad) return 3;
-    const uint64_t ax = x & 0x7fffffffffffffffull, ay = y & 0x7fffffffffffffffull, inf = 0x7ff0000000000000ull;
-    if (ax > inf || ay > inf) return (ax > inf && ay > inf) ? 1u : 0u;
-    if (ax == 0 && ay == 0) return 1;
-    return x == y ? 1u : 0u;
-  }
-  if (ta == 5 || ta == 6) {
-    const uint64_t la = rd_uleb(a), lb = rd_uleb(b);
-    if (a.bad || b.bad || la > rd_left(a) || lb > rd_left(b)) return 3;
-    if (la != lb) return 0;
-    return bytes_eq(a.p, b.p, (uint32_t)la) ? 1u : 0u;
-  }
-  if (ta == 9) return 0;                          // a child container is named by its creating op: two ops, two ContainerIDs
-  return 2;
-}
-
-LM_KERNEL LM_ONE_WAVE_GROUPS void k_mdelta(Dev d, const DlQuery* qs, unsigned long long* win, uint8_t* out, const uint64_t* out_off, DlRes* res) {
+LM_KERNEL LM_ONE_WAVE_GROUPS void k_mdelta(Dev d, const DlQuery* qs, uint32_t* scr, uint8_t* out, const uint64_t* out_off, DlRes* res) {
   const uint32_t q = (uint32_t)lmw::bid();
   const int lane = lmw::lane();
   const DlQuery Q = qs[q];
   const uint32_t doc = Q.doc;
   const DocMeta m = d.doc[doc];
-  if (status_fatal(m.status)) { if (lane == 0) { res[q].status = m.status; res[q].len = 0; res[q].cnt = 0; } return; }
+  if (status_fatal(m.status)) { dl_finish(res, q, m.status, 0, 0, 0); return; }
   int32_t err = res[q].status;   // (k_mdelta_mark: a write whose key the table does not hold)
-  const uint32_t cap = Q.n_words, list_cap = Q.n_bits;
-  const unsigned long long* winV = win + Q.bits0;
+  const uint32_t cap = Q.cap, list_cap = cap / 2;
+  unsigned long long* winV = dl_win(scr, Q);
   const unsigned long long* winA = winV + cap;
-  unsigned long long* pfx = win + Q.bits0 + 2ull * cap;
+  unsigned long long* pfx = winV + 2ull * cap;
   uint32_t* lst = (uint32_t*)(pfx + cap);
   const unsigned long long* keys = d.ht_key + d.ht0[doc];
   const unsigned long long* best = d.ht_best + d.ht0[doc];
   const uint32_t* claimed = d.ht_list + 2 * d.ht0[doc];
   uint32_t n_claimed = cap ? d.ht_cnt[doc] : 0u;
   if (cap != d.ht_cap[doc] || n_claimed > cap / 2) { err = err ? err : (int32_t)ST_UNSUPPORTED; n_claimed = 0; }
-  // the winning row of a packed word and where its value lies
-  auto row_of = [&](unsigned long long w) -> uint32_t { return (uint32_t)((w - 1) & 0xffffffu); };
   // ---- classes, 64 claimed slots per step; the changed ones into the list
   uint32_t K = 0, undecided = 0;
   for (uint32_t c0 = 0; c0 < n_claimed && !err; c0 += 64) {
@@ -163,7 +116,7 @@ LM_KERNEL LM_ONE_WAVE_GROUPS void k_mdelta(Dev d, const DlQuery* qs, unsigned lo
           const unsigned long long wv = winV[sl], wa = winA[sl];
           if (wv != best[sl]) skew = true;                     // the self-check
           else if (wv != 0 && wa != wv) {
-            const uint32_t rv = row_of(wv), ra = wa ? row_of(wa) : 0u;
+            const uint32_t rv = dl_win_row(wv), ra = wa ? dl_win_row(wa) : 0u;
             if (rv >= m.n_op || ra >= m.n_op) bad = true;
             else {
               const bool del_v = ((d.op[m.op0 + rv].cidx_kind >> 16) & 0xff) == OK_MAP_DEL;
@@ -237,10 +190,7 @@ LM_KERNEL LM_ONE_WAVE_GROUPS void k_mdelta(Dev d, const DlQuery* qs, unsigned lo
     }
   }
   // ---- rendering, container by container
-  Sink s;
-  s.out = out + out_off[q];
-  s.pos = 0;
-  s.cap = out_off[q + 1] - out_off[q];
+  Sink s = dl_sink(out, out_off, q);
   uint32_t n_listed = 0;
   sink_byte(s, '{');
   uint32_t e = 0;
@@ -256,16 +206,7 @@ LM_KERNEL LM_ONE_WAVE_GROUPS void k_mdelta(Dev d, const DlQuery* qs, unsigned lo
     const ContRow o = d.cont[m.cid0 + cidx];
     if (n_listed) sink_byte(s, ',');
     n_listed++;
-    if (o.kind_root & 0x100) {
-      sink_lit(s, "\"cid:root-", 10);
-      sink_escaped(s, d.data + o.name_off, o.name_len);
-    } else {
-      sink_lit(s, "\"cid:", 5);
-      sink_i64(s, (int64_t)(int32_t)o.counter);
-      sink_byte(s, '@');
-      sink_u64(s, o.peer < m.n_peers ? d.peer_uniq[m.praw0 + o.peer] : 0ull);
-    }
-    sink_lit(s, ":Map\":{\"updated\":{", 18);
+    sink_cid_key(s, d, m, o, ":Map\":{\"updated\":{", 18);
     for (int pass = 0; pass < 2 && !err; pass++) {
       bool first = true;
       for (uint32_t b0 = e; b0 < g1 && !err; b0 += 64) {
@@ -277,7 +218,7 @@ LM_KERNEL LM_ONE_WAVE_GROUPS void k_mdelta(Dev d, const DlQuery* qs, unsigned lo
         if (act) {
           const uint32_t sl = lst[i];
           const uint32_t krow = (uint32_t)keys[sl];
-          g_row = m.op0 + row_of(winV[sl]);
+          g_row = m.op0 + dl_win_row(winV[sl]);
           is_del = ((d.op[g_row].cidx_kind >> 16) & 0xff) == OK_MAP_DEL;
           const uint64_t ko = d.key_off[krow];
           g_koff_lo = (uint32_t)ko; g_koff_hi = (uint32_t)(ko >> 32); g_klen = d.key_len[krow];
@@ -299,22 +240,10 @@ LM_KERNEL LM_ONE_WAVE_GROUPS void k_mdelta(Dev d, const DlQuery* qs, unsigned lo
           const uint64_t limo = ((uint64_t)lmw::bcast(g_lim_hi, l) << 32) | lmw::bcast(g_lim_lo, l);
           if (voff >= limo) { err = ST_DATA_CORRUPTION; break; }
           Rd r = rd_make(d.data + voff, limo - voff);
-          if (*r.p == 9) {   // a child container created by the winning set: LoroValue::Container, never its content
-            (void)rd_u8(r);
-            const uint32_t child = rd_u8(r);
+          uint32_t child;
+          if (rd_child(r, child)) {   // a child container created by the winning set
             const OpRow wr = d.op[row];
-            const uint32_t wp = d.chg[wr.chg].peer;
-            sink_lit(s, "\"\xF0\x9F\xA6\x9C:cid:", 10);
-            sink_i64(s, (int64_t)wr.ctr);
-            sink_byte(s, '@');
-            sink_u64(s, wp < m.n_peers ? d.peer_uniq[m.praw0 + wp] : 0ull);
-            if (child == CK_MAP) sink_lit(s, ":Map\"", 5);
-            else if (child == CK_LIST) sink_lit(s, ":List\"", 6);
-            else if (child == CK_TEXT) sink_lit(s, ":Text\"", 6);
-            else if (child == CK_TREE) sink_lit(s, ":Tree\"", 6);
-            else if (child == CK_MOVABLE) sink_lit(s, ":MovableList\"", 13);
-            else if (child == CK_COUNTER) sink_lit(s, ":Counter\"", 9);
-            else err = ST_UNSUPPORTED;
+            sink_child_cid(s, d, m, d.chg[wr.chg].peer, wr.ctr, child, err);
             continue;
           }
           sink_value(s, r, err, d, vblk, m.blk0, m.n_blk);
@@ -326,13 +255,7 @@ LM_KERNEL LM_ONE_WAVE_GROUPS void k_mdelta(Dev d, const DlQuery* qs, unsigned lo
     e = g1;
   }
   sink_byte(s, '}');
-  if (s.pos > 0xfffffff0ull) err = ST_UNSUPPORTED;
-  if (lane == 0) {
-    res[q].status = err ? err : (int32_t)ST_OK;
-    res[q].len = err ? 0u : (uint32_t)s.pos;   // (s.pos > s.cap: the host sees the size and launches again with room for it)
-    res[q].cnt = n_listed;
-    if (!err && undecided) res[q].other_changed |= undecided;
-  }
+  dl_finish(res, q, err, s.pos, n_listed, undecided);
 }
 
 }  // namespace lm

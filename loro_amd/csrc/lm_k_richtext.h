@@ -232,6 +232,21 @@ LM_DEV void sink_u64(Sink& s, uint64_t u) {
   s.pos += n;
 }
 
+// the key of a container's member and what follows it: the opening quote, cid:root-<name> or cid:<counter>@<peer> (ContainerID
+// Display), then `suffix`; k_richtext and the three delta kernels (lm_k_delta*.h)
+LM_DEV void sink_cid_key(Sink& s, const Dev& d, const DocMeta& m, const ContRow& o, const char* suffix, uint32_t n) {
+  if (o.kind_root & 0x100) {
+    sink_lit(s, "\"cid:root-", 10);
+    sink_escaped(s, d.data + o.name_off, o.name_len);
+  } else {
+    sink_lit(s, "\"cid:", 5);
+    sink_i64(s, (int64_t)(int32_t)o.counter);
+    sink_byte(s, '@');
+    sink_u64(s, o.peer < m.n_peers ? d.peer_uniq[m.praw0 + o.peer] : 0ull);
+  }
+  sink_lit(s, suffix, n);
+}
+
 // visible elements of a sequence container in order, 64 per step: f(has, g) — g = element slot inside the document — is called by
 // all lanes together; lane order is sequence order
 template <class F>
@@ -331,16 +346,7 @@ LM_DEV void richtext_doc(const Dev& d, uint8_t* out, const uint64_t* out_off, ui
     if (!first_cont) sink_byte(s, ',');
     first_cont = false;
     n_listed++;
-    if (o.kind_root & 0x100) {
-      sink_lit(s, "\"cid:root-", 10);
-      sink_escaped(s, d.data + o.name_off, o.name_len);
-    } else {
-      sink_lit(s, "\"cid:", 5);
-      sink_i64(s, (int64_t)(int32_t)o.counter);
-      sink_byte(s, '@');
-      sink_u64(s, d.peer_uniq[m.praw0 + o.peer]);
-    }
-    sink_lit(s, ":Text\":[", 8);
+    sink_cid_key(s, d, m, o, ":Text\":[", 8);
     lmw::mem_fence();
     lmw::block_sync();
     // ---- walk B

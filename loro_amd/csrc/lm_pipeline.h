@@ -14,6 +14,7 @@
 #include <cstdint>
 #include <cstring>
 #include <cstdlib>
+#include <functional>
 #include <string>
 #include <vector>
 #include <stdexcept>
@@ -1824,15 +1825,14 @@ struct Engine {
     for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
   }
 
-  // ---- lm_delta (lm_k_delta.h): the Text / List deltas from a version A (the query's from_vv) to the version the last run rendered.
-  // The host parses and validates A, takes V from the version vector the run rendered, hands both to the device as per-peer-index
-  // counters, sizes two bitmaps per query from the document's element slots, and launches k_delta_mark (op rows -> deleted-in-A /
-  // deleted-in-V bits) and k_delta (one wave per query) into optimistic slabs — twice the document's JSON + a few KB; a query that
-  // needs more sends the call's queries through k_delta once more at exact sizes (the bitmaps are kept).  Only what was written
-  // crosses to the host: the result rows (16 bytes per query), then k_delta_pack moves the queries' bytes out of their slabs into one
-  // dense buffer (16-byte aligned pieces at the exclusive scan of the sizes) and that buffer comes back in one copy — dl_d2h_bytes
-  // counts both.  LM_DELTA_SKEW=1 (tests of the self-check only) hands the device a V that is one counter short for every peer:
-  // the status words then disagree with the id sets and every such query must come back LM_UNSUPPORTED.
+  // ---- lm_delta, lm_delta_map, lm_delta_movable (lm_k_delta.h, lm_k_delta_map.h, lm_k_delta_movable.h): what changed from a version A
+  // (the query's from_vv) to the version V the last run rendered, one driver (delta_run) and a policy per call.  The host parses and
+  // validates A, takes V from the version vector the run rendered and hands both to the device as per-peer-index counters
+  // (delta_bounds); it sizes and clears the queries' scratch (DlQuery), launches the call's *_mark kernel over the op rows and then its
+  // render kernel (one wave per query) into optimistic slabs; a query that needs more sends the call's queries through the render
+  // kernel once more at exact sizes (the scratch is kept).  Only what was written crosses to the host: the result rows (16 bytes per
+  // query), then k_delta_pack moves the queries' bytes out of their slabs into one dense buffer (16-byte aligned pieces at the
+  // exclusive scan of the sizes) and that buffer comes back in one copy — dl_d2h_bytes counts both.
   struct DeltaIn { uint32_t doc; const uint8_t* vv; size_t vv_len; };
   struct DeltaOut { int32_t status = ST_OK; uint32_t other_changed = 0; std::vector<uint8_t> json; };
   // VersionVector::encode (postcard: n, then peer u64 / counter i32 as LEB128, zigzag): false when the bytes are not one
@@ -1858,7 +1858,7 @@ struct Engine {
     }
     return at == n;
   }
-  // what lm_delta and lm_delta_map share: the document's peer table and the version the run rendered (once per call and document), the
+  // the document's peer table and the version the run rendered (once per call and document), the
   // query's from_vv parsed and mapped to per-peer-index bounds.  false: `o` is the query's answer (a status); true: a[] = A per peer index, dip = the document's peers and V
   struct DeltaDoc { std::vector<uint64_t> peers; std::vector<uint32_t> V; int32_t status = ST_OK; };
   bool delta_bounds(const DeltaIn& q, const char* who, std::map<uint32_t, DeltaDoc>& info, std::vector<uint8_t>& buf, DeltaOut& o, std::vector<uint32_t>& a, const DeltaDoc*& dip) {
@@ -1900,75 +1900,85 @@ struct Engine {
     }
     return true;
   }
-  void delta(const std::vector<DeltaIn>& in, int units, std::vector<DeltaOut>& out) {
+  // what differs between the three calls
+  struct DeltaPolicy {
+    const char* who;
+    bool skew_empty_v;   // LM_DELTA_SKEW=1 (tests of the kernels' self-checks only: every launched query must come back LM_UNSUPPORTED) hands the
+                         // device an EMPTY V, so that no row competes; false: a V one counter short for every peer beyond A, so that the
+                         // status words disagree with the id sets
+    bool oc_bits;        // other_changed is the render kernel's bits, not 0 / 1
+    // the answers given without a launch: true = `o` is the query's answer.  fused: an LWW Map document decoded without op rows, Maps only
+    std::function<bool(const DocMeta& m, bool fused, const std::vector<uint32_t>& a, const DeltaDoc& di, DeltaOut& o)> early;
+    // q.cap / q.n_words / q.n_bits, the 32-bit words of the query's scratch and the optimistic size of its slab
+    std::function<void(uint32_t doc, const DocMeta& m, DlQuery& q, uint64_t& scr_words, uint64_t& slab)> size;
+    std::function<void(const Dev& d, uint32_t blocks, uint32_t nq)> mark;   // launches the *_mark kernel
+    std::function<void(const Dev& d, uint32_t nq)> render;                  // launches the render kernel and closes its timing
+  };
+  static bool delta_skew() { return getenv("LM_DELTA_SKEW") != nullptr; }
+  uint32_t delta_table_cap(uint32_t doc) const { return doc < h_ht_cap.size() ? h_ht_cap[doc] : 0u; }
+  void delta_bitmaps(uint32_t doc, DlQuery& q) const {   // two bitmaps over the document's element slots
+    q.n_bits = h_doc[doc].atoms;
+    if (resident && doc < tk_elem_cap.size() && tk_elem_cap[doc] > q.n_bits) q.n_bits = tk_elem_cap[doc];
+    q.n_words = q.n_bits / 32 + 1;
+  }
+  void delta_run(const std::vector<DeltaIn>& in, std::vector<DeltaOut>& out, const DeltaPolicy& pol) {
     lmbe::bind(sc);
-    if (!ran) throw std::runtime_error("lm_delta before lm_run");
-    if (shared_mode != 0) throw std::runtime_error("lm_delta: a folded batch has to be unfolded first");
+    if (!ran) throw std::runtime_error(std::string(pol.who) + " before lm_run");
+    if (shared_mode != 0) throw std::runtime_error(std::string(pol.who) + ": a folded batch has to be unfolded first");
     out.assign(in.size(), DeltaOut());
     dl_times.clear();
     dl_launches = 0;
+    dl_d2h_bytes = 0;
     std::map<uint32_t, DeltaDoc> info;
     std::vector<uint32_t> idx, bnd;
     std::vector<DlQuery> qs;
     std::vector<uint64_t> off(1, 0);
     uint64_t words = 0;
     uint32_t blocks = 0;
-    const bool skew = getenv("LM_DELTA_SKEW") != nullptr;
-    dl_d2h_bytes = 0;
+    const bool skew = delta_skew();
     std::vector<uint8_t> buf;
     for (size_t k = 0; k < in.size(); k++) {
       const uint32_t doc = in[k].doc;
-      DeltaOut& o = out[k];
       std::vector<uint32_t> a;
       const DeltaDoc* dip = nullptr;
-      if (!delta_bounds(in[k], "lm_delta", info, buf, o, a, dip)) continue;
+      if (!delta_bounds(in[k], pol.who, info, buf, out[k], a, dip)) continue;
       const DocMeta& m = h_doc[doc];
-      const DeltaDoc& di = *dip;
-      if (doc < h_fused.size() && h_fused[doc]) {   // an LWW Map document decoded without op rows: Maps only
-        for (uint32_t p = 0; p < m.n_peers; p++) if (di.V[p] > a[p]) o.other_changed = 1u;
-        o.json = {'{', '}'};
-        continue;
-      }
+      if (pol.early(m, doc < h_fused.size() && h_fused[doc], a, *dip, out[k])) continue;
       DlQuery q;
       memset(&q, 0, sizeof q);
       q.doc = doc; q.n_bnd = m.n_peers; q.bnd0 = bnd.size();
       bnd.insert(bnd.end(), a.begin(), a.end());
-      bnd.insert(bnd.end(), di.V.begin(), di.V.end());
-      if (skew) for (uint32_t p = 0; p < m.n_peers; p++) if (bnd[bnd.size() - m.n_peers + p] > a[p]) bnd[bnd.size() - m.n_peers + p]--;
-      q.n_bits = m.atoms;
-      if (resident && doc < tk_elem_cap.size() && tk_elem_cap[doc] > q.n_bits) q.n_bits = tk_elem_cap[doc];
-      q.n_words = q.n_bits / 32 + 1;
-      q.bits0 = words;
-      words += 2ull * q.n_words;
+      for (uint32_t p = 0; p < m.n_peers; p++) {
+        const uint32_t v = dip->V[p];
+        bnd.push_back(!skew ? v : pol.skew_empty_v ? 0u : v - (v > a[p] ? 1u : 0u));
+      }
+      uint64_t scr_words = 0, slab = 0;
+      pol.size(doc, m, q, scr_words, slab);
+      q.scr0 = words;
+      words += (scr_words + 1) & ~1ull;
       q.row_blk0 = blocks;
       blocks += cdiv(m.n_op, 64);
-      const uint64_t cap = 2ull * m.out_len + 64ull * m.n_cont + 1024;
-      off.push_back(off.back() + ((cap + 15) & ~15ull));
+      off.push_back(off.back() + ((slab + 15) & ~15ull));
       qs.push_back(q);
       idx.push_back((uint32_t)k);
     }
     if (qs.empty()) return;
     const size_t nq = qs.size();
     bnd.push_back(0);
-    b_dl_q.ensure(nq * sizeof(DlQuery)); b_dl_bnd.ensure(bnd.size() * 4); b_dl_bits.ensure((words + 1) * 4); b_dl_res.ensure(nq * sizeof(DlRes));
+    b_dl_q.ensure(nq * sizeof(DlQuery)); b_dl_bnd.ensure(bnd.size() * 4); b_dl_bits.ensure((words + 2) * 4); b_dl_res.ensure(nq * sizeof(DlRes));
     lmbe::h2d(b_dl_q.p, qs.data(), nq * sizeof(DlQuery));
     lmbe::h2d(b_dl_bnd.p, bnd.data(), bnd.size() * 4);
-    lmbe::dmemset(b_dl_bits.p, 0, (words + 1) * 4);
+    lmbe::dmemset(b_dl_bits.p, 0, (words + 2) * 4);
     lmbe::dmemset(b_dl_res.p, 0, nq * sizeof(DlRes));
     Dev d = last_d;
     lmbe::reset_times();
     if (blocks) {
       lmbe::tic(profiling);
-      LM_LAUNCH(k_delta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (uint32_t)nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_res.as<DlRes>());
-      lmbe::toc("k_delta_mark", dl_times, profiling);
+      pol.mark(d, blocks, (uint32_t)nq);
     }
-    delta_slabs(off, idx, out, false, [&]() {
-      LM_LAUNCH(k_delta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), (const uint32_t*)b_dl_bits.as<uint32_t>(), b_dl_out.as<uint8_t>(),
-                (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>(), units);
-      lmbe::toc("k_delta", dl_times, profiling);
-    });
+    delta_slabs(off, idx, out, pol.oc_bits, [&]() { pol.render(d, (uint32_t)nq); });
   }
-  // the second half of lm_delta / lm_delta_map: `launch` renders the queries into the slabs of `off` (it closes its own timing), once
+  // the second half of delta_run: `launch` renders the queries into the slabs of `off` (it closes its own timing), once
   // more at exact sizes when a slab was too small; then the written bytes are packed, copied back and handed to the queries' answers
   template <class L> void delta_slabs(std::vector<uint64_t>& off, const std::vector<uint32_t>& idx, std::vector<DeltaOut>& out, bool oc_bits, L launch) {
     const size_t nq = idx.size();
@@ -2019,150 +2029,86 @@ struct Engine {
     }
   }
 
-  // ---- lm_delta_map (lm_k_delta_map.h): the Map deltas from a version A to the version the last run rendered.  A and V reach the
-  // device as lm_delta's do (delta_bounds); per query the device gets three 64-bit words per slot of the document's LWW table (winner at
-  // V, winner at A, key prefix) and a sort list of half as many entries, all cleared here.  k_mdelta_mark raises the winners from the op
-  // rows, k_mdelta checks the winner at V against the table the run left, classifies, sorts and renders into optimistic slabs (half the
-  // document's JSON + a few KB: the Maps' whole content from the empty version takes the second launch); the
-  // second launch, the packing and lm_delta_bytes are lm_delta's (delta_slabs).  LM_DELTA_SKEW=1 (tests of the self-check only) hands
-  // the device an EMPTY V: no row competes, every claimed slot's winner differs from the table's and every query on a document with a
-  // Map write must come back LM_UNSUPPORTED.  A document decoded without op rows (h_fused) cannot be answered here: the context runs
-  // its part once more through the row tables first (no_map_fused).
+  // lm_delta: Text and List.  Two bitmaps per query; slabs of twice the document's JSON + a few KB
+  void delta(const std::vector<DeltaIn>& in, int units, std::vector<DeltaOut>& out) {
+    DeltaPolicy pol{"lm_delta", false, false};
+    pol.early = [&](const DocMeta& m, bool fused, const std::vector<uint32_t>& a, const DeltaDoc& di, DeltaOut& o) {
+      if (!fused) return false;
+      for (uint32_t p = 0; p < m.n_peers; p++) if (di.V[p] > a[p]) o.other_changed = 1u;
+      o.json = {'{', '}'};
+      return true;
+    };
+    pol.size = [&](uint32_t doc, const DocMeta& m, DlQuery& q, uint64_t& scr_words, uint64_t& slab) {
+      delta_bitmaps(doc, q);
+      scr_words = 2ull * q.n_words;
+      slab = 2ull * m.out_len + 64ull * m.n_cont + 1024;
+    };
+    pol.mark = [&](const Dev& d, uint32_t blocks, uint32_t nq) {
+      LM_LAUNCH(k_delta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_res.as<DlRes>());
+      lmbe::toc("k_delta_mark", dl_times, profiling);
+    };
+    pol.render = [&](const Dev& d, uint32_t nq) {
+      LM_LAUNCH(k_delta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_out.as<uint8_t>(),
+                (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>(), units);
+      lmbe::toc("k_delta", dl_times, profiling);
+    };
+    delta_run(in, out, pol);
+  }
+  // lm_delta_map: Map.  Per slot of the document's LWW table three 64-bit words (winner at V, winner at A, key prefix) and a sort list of
+  // half as many entries; slabs of half the document's JSON + a few KB (a subscriber rarely lacks more than half the document: the Maps'
+  // whole content from the empty version takes the second launch).  A document decoded without op rows (h_fused) cannot be answered
+  // here: the context runs its part once more through the row tables first (no_map_fused)
   void delta_map(const std::vector<DeltaIn>& in, std::vector<DeltaOut>& out) {
-    lmbe::bind(sc);
-    if (!ran) throw std::runtime_error("lm_delta_map before lm_run");
-    if (shared_mode != 0) throw std::runtime_error("lm_delta_map: a folded batch has to be unfolded first");
-    out.assign(in.size(), DeltaOut());
-    dl_times.clear();
-    dl_launches = 0;
-    dl_d2h_bytes = 0;
-    std::map<uint32_t, DeltaDoc> info;
-    std::vector<uint32_t> idx, bnd;
-    std::vector<DlQuery> qs;
-    std::vector<uint64_t> off(1, 0);
-    uint64_t words = 0;
-    uint32_t blocks = 0;
-    const bool skew = getenv("LM_DELTA_SKEW") != nullptr;
-    std::vector<uint8_t> buf;
-    for (size_t k = 0; k < in.size(); k++) {
-      const uint32_t doc = in[k].doc;
-      DeltaOut& o = out[k];
-      std::vector<uint32_t> a;
-      const DeltaDoc* dip = nullptr;
-      if (!delta_bounds(in[k], "lm_delta_map", info, buf, o, a, dip)) continue;
-      const DocMeta& m = h_doc[doc];
-      if (doc < h_fused.size() && h_fused[doc]) throw std::runtime_error("lm_delta_map: a document decoded without op rows was not run again");
-      if (!skew && a == dip->V) { o.json = {'{', '}'}; continue; }   // A == V
-      DlQuery q;
-      memset(&q, 0, sizeof q);
-      q.doc = doc; q.n_bnd = m.n_peers; q.bnd0 = bnd.size();
-      bnd.insert(bnd.end(), a.begin(), a.end());
-      if (skew) bnd.insert(bnd.end(), m.n_peers, 0u); else bnd.insert(bnd.end(), dip->V.begin(), dip->V.end());
-      const uint32_t cap = doc < h_ht_cap.size() ? h_ht_cap[doc] : 0u;
-      q.n_words = cap; q.n_bits = cap / 2;
-      q.bits0 = words;
-      words += 3ull * cap + cap / 4 + 1;
-      q.row_blk0 = blocks;
-      blocks += cdiv(m.n_op, 64);
-      const uint64_t slab = m.out_len / 2 + 64ull * m.n_cont + 1024;   // (optimistic: a subscriber rarely lacks more than half the document)
-      off.push_back(off.back() + ((slab + 15) & ~15ull));
-      qs.push_back(q);
-      idx.push_back((uint32_t)k);
-    }
-    if (qs.empty()) return;
-    const size_t nq = qs.size();
-    bnd.push_back(0);
-    b_dl_q.ensure(nq * sizeof(DlQuery)); b_dl_bnd.ensure(bnd.size() * 4); b_dl_bits.ensure((words + 1) * 8); b_dl_res.ensure(nq * sizeof(DlRes));
-    lmbe::h2d(b_dl_q.p, qs.data(), nq * sizeof(DlQuery));
-    lmbe::h2d(b_dl_bnd.p, bnd.data(), bnd.size() * 4);
-    lmbe::dmemset(b_dl_bits.p, 0, (words + 1) * 8);
-    lmbe::dmemset(b_dl_res.p, 0, nq * sizeof(DlRes));
-    Dev d = last_d;
-    lmbe::reset_times();
-    if (blocks) {
-      lmbe::tic(profiling);
-      LM_LAUNCH(k_mdelta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (uint32_t)nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<unsigned long long>(), b_dl_res.as<DlRes>(),
+    DeltaPolicy pol{"lm_delta_map", true, true};
+    pol.early = [&](const DocMeta&, bool fused, const std::vector<uint32_t>& a, const DeltaDoc& di, DeltaOut& o) {
+      if (fused) throw std::runtime_error("lm_delta_map: a document decoded without op rows was not run again");
+      if (delta_skew() || a != di.V) return false;
+      o.json = {'{', '}'};   // A == V
+      return true;
+    };
+    pol.size = [&](uint32_t doc, const DocMeta& m, DlQuery& q, uint64_t& scr_words, uint64_t& slab) {
+      q.cap = delta_table_cap(doc);
+      scr_words = 6ull * q.cap + q.cap / 2;
+      slab = m.out_len / 2 + 64ull * m.n_cont + 1024;
+    };
+    pol.mark = [&](const Dev& d, uint32_t blocks, uint32_t nq) {
+      LM_LAUNCH(k_mdelta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_res.as<DlRes>(),
                 (kn.lww_lds && !resident) ? 1u : 0u);
       lmbe::toc("k_mdelta_mark", dl_times, profiling);
-    }
-    delta_slabs(off, idx, out, true, [&]() {
-      LM_LAUNCH(k_mdelta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), b_dl_bits.as<unsigned long long>(), b_dl_out.as<uint8_t>(), (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>());
+    };
+    pol.render = [&](const Dev& d, uint32_t nq) {
+      LM_LAUNCH(k_mdelta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), b_dl_bits.as<uint32_t>(), b_dl_out.as<uint8_t>(), (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>());
       lmbe::toc("k_mdelta", dl_times, profiling);
-    });
+    };
+    delta_run(in, out, pol);
   }
-
-  // ---- lm_delta_movable (lm_k_delta_movable.h): the MovableList deltas from a version A to the version the last run rendered.  A and V
-  // reach the device as lm_delta's do (delta_bounds); per query the device gets two 64-bit winner words per slot of the document's
-  // table (at V, at A) and two bitmaps over the document's element slots (gone at A, gone at V), all cleared here.  k_mldelta_mark fills
-  // them from the op rows, k_mldelta checks them against the status words and the table the run left, classifies and renders into
-  // optimistic slabs (twice the document's JSON + a few KB); the second launch, the packing and lm_delta_bytes are lm_delta's (delta_slabs).
-  // LM_DELTA_SKEW=1 (tests of the self-check only) hands the device a V that is one counter short for every peer, as in delta().  An LWW
-  // Map document decoded without op rows holds no MovableList: answered here, as is a document with neither DF_MOVABLE nor DF_SOFT_UNSUPPORTED.
+  // lm_delta_movable: MovableList.  Two 64-bit winner words per slot of the document's table (at V, at A) and lm_delta's two bitmaps
+  // (gone at A, gone at V); lm_delta's slabs (a delta of single-item ops is larger than the values it moves).  An LWW Map document decoded
+  // without op rows holds no MovableList: answered here, as is a document with neither DF_MOVABLE nor DF_SOFT_UNSUPPORTED — no
+  // MovableList, and no applied Tree / Counter op that bit 0 could report (k_map_lww / k_map_lww_doc flag every one)
   void delta_movable(const std::vector<DeltaIn>& in, std::vector<DeltaOut>& out) {
-    lmbe::bind(sc);
-    if (!ran) throw std::runtime_error("lm_delta_movable before lm_run");
-    if (shared_mode != 0) throw std::runtime_error("lm_delta_movable: a folded batch has to be unfolded first");
-    out.assign(in.size(), DeltaOut());
-    dl_times.clear();
-    dl_launches = 0;
-    dl_d2h_bytes = 0;
-    std::map<uint32_t, DeltaDoc> info;
-    std::vector<uint32_t> idx, bnd;
-    std::vector<DlQuery> qs;
-    std::vector<uint64_t> off(1, 0);
-    uint64_t words = 0;
-    uint32_t blocks = 0;
-    const bool skew = getenv("LM_DELTA_SKEW") != nullptr;
-    std::vector<uint8_t> buf;
-    for (size_t k = 0; k < in.size(); k++) {
-      const uint32_t doc = in[k].doc;
-      DeltaOut& o = out[k];
-      std::vector<uint32_t> a;
-      const DeltaDoc* dip = nullptr;
-      if (!delta_bounds(in[k], "lm_delta_movable", info, buf, o, a, dip)) continue;
-      const DocMeta& m = h_doc[doc];
-      if ((doc < h_fused.size() && h_fused[doc]) || a == dip->V) { o.json = {'{', '}'}; continue; }   // Maps only; A == V
-      // no MovableList, and no applied Tree / Counter op that bit 0 could report (k_map_lww / k_map_lww_doc flag every one): nothing to launch
-      if (!(m.flags & (DF_MOVABLE | DF_SOFT_UNSUPPORTED))) { o.json = {'{', '}'}; continue; }
-      DlQuery q;
-      memset(&q, 0, sizeof q);
-      q.doc = doc; q.n_bnd = m.n_peers; q.bnd0 = bnd.size();
-      bnd.insert(bnd.end(), a.begin(), a.end());
-      bnd.insert(bnd.end(), dip->V.begin(), dip->V.end());
-      if (skew) for (uint32_t p = 0; p < m.n_peers; p++) if (bnd[bnd.size() - m.n_peers + p] > a[p]) bnd[bnd.size() - m.n_peers + p]--;
-      q.n_bits = m.atoms;
-      if (resident && doc < tk_elem_cap.size() && tk_elem_cap[doc] > q.n_bits) q.n_bits = tk_elem_cap[doc];
-      q.n_words = q.n_bits / 32 + 1;
-      q.pad = doc < h_ht_cap.size() ? h_ht_cap[doc] : 0u;
-      q.bits0 = words;
-      words += 2ull * q.pad + q.n_words;   // (two bitmaps of n_words 32-bit words)
-      q.row_blk0 = blocks;
-      blocks += cdiv(m.n_op, 64);
-      const uint64_t slab = 2ull * m.out_len + 64ull * m.n_cont + 1024;   // (lm_delta's: a delta of single-item ops is larger than the values it moves)
-      off.push_back(off.back() + ((slab + 15) & ~15ull));
-      qs.push_back(q);
-      idx.push_back((uint32_t)k);
-    }
-    if (qs.empty()) return;
-    const size_t nq = qs.size();
-    bnd.push_back(0);
-    b_dl_q.ensure(nq * sizeof(DlQuery)); b_dl_bnd.ensure(bnd.size() * 4); b_dl_bits.ensure((words + 1) * 8); b_dl_res.ensure(nq * sizeof(DlRes));
-    lmbe::h2d(b_dl_q.p, qs.data(), nq * sizeof(DlQuery));
-    lmbe::h2d(b_dl_bnd.p, bnd.data(), bnd.size() * 4);
-    lmbe::dmemset(b_dl_bits.p, 0, (words + 1) * 8);
-    lmbe::dmemset(b_dl_res.p, 0, nq * sizeof(DlRes));
-    Dev d = last_d;
-    lmbe::reset_times();
-    if (blocks) {
-      lmbe::tic(profiling);
-      LM_LAUNCH(k_mldelta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (uint32_t)nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<unsigned long long>(), b_dl_res.as<DlRes>());
+    DeltaPolicy pol{"lm_delta_movable", false, true};
+    pol.early = [&](const DocMeta& m, bool fused, const std::vector<uint32_t>& a, const DeltaDoc& di, DeltaOut& o) {
+      if (!fused && a != di.V && (m.flags & (DF_MOVABLE | DF_SOFT_UNSUPPORTED))) return false;
+      o.json = {'{', '}'};
+      return true;
+    };
+    pol.size = [&](uint32_t doc, const DocMeta& m, DlQuery& q, uint64_t& scr_words, uint64_t& slab) {
+      delta_bitmaps(doc, q);
+      q.cap = delta_table_cap(doc);
+      scr_words = 4ull * q.cap + 2ull * q.n_words;
+      slab = 2ull * m.out_len + 64ull * m.n_cont + 1024;
+    };
+    pol.mark = [&](const Dev& d, uint32_t blocks, uint32_t nq) {
+      LM_LAUNCH(k_mldelta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_res.as<DlRes>());
       lmbe::toc("k_mldelta_mark", dl_times, profiling);
-    }
-    delta_slabs(off, idx, out, true, [&]() {
-      LM_LAUNCH(k_mldelta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), (const unsigned long long*)b_dl_bits.as<unsigned long long>(), b_dl_out.as<uint8_t>(),
+    };
+    pol.render = [&](const Dev& d, uint32_t nq) {
+      LM_LAUNCH(k_mldelta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_out.as<uint8_t>(),
                 (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>());
       lmbe::toc("k_mldelta", dl_times, profiling);
-    });
+    };
+    delta_run(in, out, pol);
   }
 
   // ---- lm_export: the updates document `i` holds beyond `from_vv` (lm_export.h).  The blobs come back from the arena, the
