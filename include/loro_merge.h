@@ -372,7 +372,7 @@ int lm_cursor_at(lm_ctx* ctx, const lm_cursor_at_query* queries, size_t n, lm_cu
  * inlined, its delta stands under its own key.  With units == 1 a Text retain / delete counts one more per scalar >= U+10000.
  * Result bytes of a query: one JSON object {"<ContainerID Display>":[op,...],...} over every Text / List container of the document
  * whose delta is not empty, members in the bytewise order of their JSON-encoded keys (lm_richtext_result's rule); {} when nothing
- * changed.  Attributes are out of scope: lm_richtext gives the styles at V.
+ * changed.  Attributes are out of scope: lm_richtext gives the styles at V, lm_delta_richtext below the delta with attributes.
  *
  * Statuses: LM_FRONTIERS_NOT_FOUND — some A[p] > V[p], or A names a peer the document does not know with a counter > 0;
  * LM_UNSUPPORTED — the document has no rendering (an engine limit), or the kernel's self-check failed ("visible by status" must
@@ -479,6 +479,45 @@ int lm_delta_map(lm_ctx* ctx, const lm_delta_query* queries, size_t n, lm_delta_
  * lm_delta_bytes reports the bytes of whichever of lm_delta / lm_delta_map / lm_delta_movable ran last; `json` is valid until the next
  * of these calls / lm_stage / lm_destroy.  The call changes nothing a run wrote: lm_fetch gives the same bytes afterwards. */
 int lm_delta_movable(lm_ctx* ctx, const lm_delta_query* queries, size_t n, lm_delta_result* out);
+
+/* ---- Text deltas WITH STYLE ATTRIBUTES from a version to the rendered one: what the TextDelta events of subscribe tell a rich-text
+ * subscriber — lm_delta's answer for the Text containers, its retains and inserts carrying attributes.  The call is to lm_delta what
+ * lm_richtext is to lm_fetch; answered on the device from the trackers, the anchors' StyleOps and the op rows of the last lm_run
+ * (k_rtdelta_mark, k_rtdelta: loro_amd/csrc/lm_k_delta_richtext.h).  lm_delta's query and result structs, `units`, valid states, -1
+ * cases, batch shapes and the lifetime of `json`.  Text containers only.  A = from_vv, V = the version that run rendered.
+ *
+ * Definition, by id sets, for one Text container; its elements, anchors included, stand in the tracker's sequence order.
+ *   - Scalars are classed K / I / D / skipped exactly as lm_delta classes them.  Anchors are never elements of a delta.
+ *   - A MARK is a StyleStart anchor (p, c) together with its StyleEnd (p, c + 1); it carries the StyleOp (key, value, lamport, peer)
+ *     of the Start.  It is live at A iff both anchors are in A by lm_delta's own test (counter below A[p], no delete atom in A
+ *     targets the slot); live at V iff both anchors are visible; in both cases the End stands behind the Start.  A version that
+ *     contains the Start and not the End has no such mark.
+ *   - attrs_X(s), X one of A / V, for a scalar s: per key, the value of the mark live at X with the greatest (lamport, peer id) among
+ *     those whose Start stands in front of s and whose End stands behind it; a key whose winner has a null value is absent.
+ *   - An I scalar carries attrs_V.  A D scalar carries nothing.  A K scalar carries its CHANGE SET: key: attrs_V[key] for every key
+ *     that attrs_A lacks or whose two values are unequal under LoroValue equality (loro-common/src/value.rs:29-44, as lm_delta_map
+ *     compares them), key: null for every key in attrs_A and not in attrs_V.  When the same op wins a key at A and at V the key is
+ *     unchanged and no values are compared.
+ * Canonical form: lm_delta's, with runs also cut by attributes.  A maximal run of K scalars — anchors and skipped elements between
+ * them do not count — whose neighbouring change sets are equal (equal key sets, equal values per key; a joined run keeps the set it
+ * was opened with) gives {"retain":n} or {"attributes":{...},"retain":n}.  A gap gives first its I scalars in sequence order, one
+ * {"insert":"..."} or {"attributes":{...},"insert":"..."} per maximal run of equal attrs_V, then at most one {"delete":n}.  A trailing
+ * retain WITHOUT attributes is dropped, one with attributes stays.  A container with an empty delta is left out; {} when nothing
+ * changed; members in the bytewise order of their JSON-encoded keys; attribute keys bytewise sorted and escaped, values in the
+ * canonical form, as lm_richtext writes them; units == 1 counts as in lm_delta.
+ * Nested values: two nested List / Map values from DIFFERENT ops are not compared on the device (the rule of lm_delta_map /
+ * lm_delta_movable): in a change set the key counts as changed and carries V's value, in a run join the runs stay apart, and bit 1 of
+ * other_changed is set — still a correct delta, only not a minimal one.
+ * other_changed of this call: bit 0 — a List, Map, MovableList, Tree or Counter container received an op whose id lies in V \ A;
+ * bit 1 — an undecided nested pair.
+ * Statuses: lm_delta's; LM_UNSUPPORTED also when more than 64 marks are live at one place at A or at V, when a Text has more than 64
+ * distinct style keys, or when lm_delta's self-check fails.
+ * Relation to the reference: its own events (richtext_state.rs:379-560) are not minimal — on a deleted anchor it annotates the whole
+ * affected range again with every style it carries, and its inserts go through to_option_map, which keeps null-valued keys.  This
+ * call gives the minimal delta, with nulls dropped from inserts; applying either to the rich-text value at A gives the rich-text
+ * value at V.  Byte equality with a Rust event is not claimed.
+ * lm_delta_bytes reports whichever delta call ran last.  The call changes nothing a run wrote. */
+int lm_delta_richtext(lm_ctx* ctx, const lm_delta_query* queries, size_t n, int units, lm_delta_result* out);
 
 /* Wave-primitive self test on the device (DPP scan, ballot ranks); returns the number of mismatches. */
 int lm_selftest(lm_ctx* ctx);

@@ -50,7 +50,7 @@ CURSOR_OK, CURSOR_DELETED, CURSOR_ID_NOT_FOUND, CURSOR_CONTAINER_NOT_FOUND, CURS
 SYMBOLS = ["create", "destroy", "last_error", "merge_batch", "stage", "run", "fetch", "get_stats", "set_profiling", "kernel_time", "selftest", "result_meta", "result_hashes", "n_streams", "run_async", "wait",
            "encode_block", "encode_updates", "free_bytes", "import", "resident_fresh", "import_modes", "import_lca", "export", "comm_unique_id", "comm_init", "summary_allgather",
            "summary_layout", "summary_rows_device", "summary_allgather_device", "shared_documents", "richtext", "richtext_result", "fused_documents", "redo_documents", "state_documents", "host_alloc", "host_free", "staged_direct",
-           "cursor_pos", "cursor_at", "delta", "delta_bytes", "delta_map", "delta_movable"]
+           "cursor_pos", "cursor_at", "delta", "delta_bytes", "delta_map", "delta_movable", "delta_richtext"]
 
 
 class Binding:
@@ -97,6 +97,8 @@ class Binding:
         self.delta_map.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeltaQuery), ctypes.c_size_t, ctypes.POINTER(DeltaResult)]
         self.delta_movable = g("delta_movable"); self.delta_movable.restype = ctypes.c_int
         self.delta_movable.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeltaQuery), ctypes.c_size_t, ctypes.POINTER(DeltaResult)]
+        self.delta_richtext = g("delta_richtext"); self.delta_richtext.restype = ctypes.c_int
+        self.delta_richtext.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeltaQuery), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(DeltaResult)]
         self.delta_bytes = g("delta_bytes"); self.delta_bytes.restype = ctypes.c_uint64; self.delta_bytes.argtypes = [ctypes.c_void_p]
         self.comm_unique_id = g("comm_unique_id"); self.comm_unique_id.restype = ctypes.c_int; self.comm_unique_id.argtypes = [ctypes.c_char_p]
         self.comm_init = g("comm_init"); self.comm_init.restype = ctypes.c_int; self.comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
@@ -343,6 +345,14 @@ class Context:
         [(status, other_changed, json bytes)] — other_changed bit 0: a Tree / Counter received an op in V \\ A, bit 1: two nested List /
         Map values the device does not compare were treated as changed.  self.b.delta_bytes(self.h) = the bytes the call copied back."""
         return self._delta(self.b.delta_movable, queries)
+
+    def delta_richtext(self, queries, units=0):
+        """lm_delta_richtext (the TextDelta events with their attributes): the Text deltas from a version to the version the last run
+        rendered, retains and inserts carrying style attributes — what lm_delta is to fetch(), this is to richtext().  queries and
+        units as for delta().  Returns [(status, other_changed, json bytes)] — other_changed bit 0: a container that is not a Text
+        received an op in V \\ A, bit 1: two nested List / Map style values of different ops, which the device does not compare,
+        were treated as unequal.  self.b.delta_bytes(self.h) = the bytes the call copied back."""
+        return self._delta(self.b.delta_richtext, queries, units)
 
     def comm_init(self, rank=0, world=1, unique_id=None):
         if self.b.comm_init(self.h, rank, world, unique_id or bytes(128)) != 0:

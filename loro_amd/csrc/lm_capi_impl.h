@@ -587,6 +587,8 @@ struct lm_ctx_impl {
   }
   // ---- lm_delta_movable (lm_k_delta_movable.h): routed like lm_delta
   void delta_movable(std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& out) { delta_route("lm_delta_movable", in, out, [&](lm::Engine& e, const std::vector<lm::Engine::DeltaIn>& sub, std::vector<lm::Engine::DeltaOut>& r) { e.delta_movable(sub, r); }); }
+  // ---- lm_delta_richtext (lm_k_delta_richtext.h): routed like lm_delta
+  void delta_richtext(std::vector<lm::Engine::DeltaIn>& in, int units, std::vector<lm::Engine::DeltaOut>& out) { delta_route("lm_delta_richtext", in, out, [&](lm::Engine& e, const std::vector<lm::Engine::DeltaIn>& sub, std::vector<lm::Engine::DeltaOut>& r) { e.delta_richtext(sub, units, r); }); }
   // `prepare`: the call's name for cursor_prepare, nullptr when the caller has done that
   template <class F> void delta_route(const char* prepare, std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& out, F call) {
     if (prepare) cursor_prepare(prepare);
@@ -1016,6 +1018,13 @@ int LM_API(delta_map)(void* c, const lm_delta_query_c* qs, size_t n, lm_delta_re
 int LM_API(delta_movable)(void* c, const lm_delta_query_c* qs, size_t n, lm_delta_result_c* out) {
   auto* x = (lm_ctx_impl*)c;
   return delta_entry(x, "lm_delta_movable", qs, n, out, [&](std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& r) { x->delta_movable(in, r); });
+}
+// ---- Text deltas with style attributes from a version to the rendered one (include/loro_merge.h): on the device, from the trackers,
+// the anchors' StyleOps and the op rows of the last lm_run (lm_k_delta_richtext.h)
+int LM_API(delta_richtext)(void* c, const lm_delta_query_c* qs, size_t n, int units, lm_delta_result_c* out) {
+  auto* x = (lm_ctx_impl*)c;
+  if (units < 0 || units > 1) { x->err = "lm_delta_richtext: units is 0 (Unicode scalars) or 1 (UTF-16 code units)"; return -1; }
+  return delta_entry(x, "lm_delta_richtext", qs, n, out, [&](std::vector<lm::Engine::DeltaIn>& in, std::vector<lm::Engine::DeltaOut>& r) { x->delta_richtext(in, units, r); });
 }
 uint64_t LM_API(delta_bytes)(void* c) { return ((lm_ctx_impl*)c)->dl_d2h_bytes; }
 int LM_API(get_stats)(void* c, lm_run_stats_c* s) {

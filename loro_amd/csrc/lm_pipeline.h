@@ -29,6 +29,7 @@
 #include "lm_k_delta.h"
 #include "lm_k_delta_map.h"
 #include "lm_k_delta_movable.h"
+#include "lm_k_delta_richtext.h"
 #include "lm_snapshot.h"
 #include "lm_export.h"
 #include "lm_snapshot_base.h"
@@ -2107,6 +2108,36 @@ struct Engine {
       LM_LAUNCH(k_mldelta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_out.as<uint8_t>(),
                 (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>());
       lmbe::toc("k_mldelta", dl_times, profiling);
+    };
+    delta_run(in, out, pol);
+  }
+  // lm_delta_richtext: Text, with style attributes.  lm_delta's two bitmaps — what an anchor needs (is its partner in A, in V) is
+  // read from them where the anchor stands, so no scratch beyond them; lm_delta's slabs plus the document's input bytes, which bound
+  // the style values a delta can repeat per container (the second launch covers a wrong guess).  An LWW Map document decoded without
+  // op rows holds no Text: answered here, as lm_delta answers it
+  void delta_richtext(const std::vector<DeltaIn>& in, int units, std::vector<DeltaOut>& out) {
+    DeltaPolicy pol{"lm_delta_richtext", false, true};
+    pol.early = [&](const DocMeta& m, bool fused, const std::vector<uint32_t>& a, const DeltaDoc& di, DeltaOut& o) {
+      if (!fused) return false;
+      for (uint32_t p = 0; p < m.n_peers; p++) if (di.V[p] > a[p]) o.other_changed = 1u;
+      o.json = {'{', '}'};
+      return true;
+    };
+    pol.size = [&](uint32_t doc, const DocMeta& m, DlQuery& q, uint64_t& scr_words, uint64_t& slab) {
+      delta_bitmaps(doc, q);
+      scr_words = 2ull * q.n_words;
+      uint64_t in_bytes = 0;
+      if (doc + 1 < h_doc_blob.size()) for (uint32_t b = h_doc_blob[doc]; b < h_doc_blob[doc + 1] && b < h_blob_len.size(); b++) in_bytes += h_blob_len[b];
+      slab = 2ull * m.out_len + 64ull * m.n_cont + 1024 + in_bytes;
+    };
+    pol.mark = [&](const Dev& d, uint32_t blocks, uint32_t nq) {
+      LM_LAUNCH(k_rtdelta_mark, blocks, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), nq, (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_res.as<DlRes>());
+      lmbe::toc("k_rtdelta_mark", dl_times, profiling);
+    };
+    pol.render = [&](const Dev& d, uint32_t nq) {
+      LM_LAUNCH(k_rtdelta, nq, 64, d, (const DlQuery*)b_dl_q.as<DlQuery>(), (const uint32_t*)b_dl_bnd.as<uint32_t>(), b_dl_bits.as<uint32_t>(), b_dl_out.as<uint8_t>(),
+                (const uint64_t*)b_dl_off.as<uint64_t>(), b_dl_res.as<DlRes>(), units);
+      lmbe::toc("k_rtdelta", dl_times, profiling);
     };
     delta_run(in, out, pol);
   }
