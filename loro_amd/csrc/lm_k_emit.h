@@ -332,6 +332,13 @@ LM_DEV void sink_lanes(Sink& s, uint64_t bytes, uint32_t n) {
   }
   s.pos += tot;
 }
+// sixteen bytes that travel together: an aligned piece of the Text renderer's LDS window, stored to the same piece of the slab
+struct alignas(16) EmitPiece { uint32_t w[4]; };
+#ifndef LM_EMU
+LM_DEV void st128(uint8_t* p, const EmitPiece& v) { *(EmitPiece*)__builtin_assume_aligned(p, 16) = v; }
+#else
+LM_DEV void st128(uint8_t* p, const EmitPiece& v) { memcpy(p, &v, 16); }   // (a host buffer promises no alignment)
+#endif
 LM_DEV char hexd(uint32_t v) { return (char)(v < 10 ? '0' + v : 'a' + (v - 10)); }
 // JSON escape of one byte of a UTF-8 string (bytes >= 0x80 pass through)
 LM_DEV void esc_byte(uint32_t c, uint64_t& bytes, uint32_t& n) {
@@ -784,8 +791,8 @@ LM_DEV void emit_doc(Dev d, int mode, int pass) {
       uint32_t cidx = s_frame[4 * (sp - 1)], fa = s_frame[4 * (sp - 1) + 1], fb = s_frame[4 * (sp - 1) + 2], fc = s_frame[4 * (sp - 1) + 3];
       uint32_t kind = d.cont[m.cid0 + cidx].kind_root & 0xff;
       if (kind == CK_TEXT && d.span) {
-        // span-granular leaves: per leaf, the visible runs are flattened 64 elements per step — lane → (run, offset)
-        // by a search over the running lengths kept in LDS; a run's elements are consecutive in tb[] — one BYTE per element:
+        // span-granular leaves: per leaf, the visible runs are flattened 256 elements per step (k_emit_any: 64) — lane → (run,
+        // offset) by a search over the running lengths kept in LDS; a run's elements are consecutive in tb[] — one BYTE per element:
         // the scalar itself when it is ASCII, TB_WIDE when cp[] holds it (a multi-byte scalar), TB_ANCHOR for a style anchor
         sink_byte(s, '"');
         uint32_t r0 = d.cont_root0[m.cid0 + cidx], nr = d.cont_nroot[m.cid0 + cidx];
@@ -821,13 +828,16 @@ LM_DEV void emit_doc(Dev d, int mode, int pass) {
           s_inc[lane] = inc;
           s_g0[lane] = vl ? s_eb[pid_peer(id0)] + pid_ctr(id0) - (inc - vl) : 0u;   // element index minus position: tb index = g0 + position
           lmw::block_sync();
-          for (uint32_t e0 = 0; e0 < total; e0 += 64 * EU) {
+          // the 64 * EU elements of the leaf from eb on (as far as they lie below ee), one element per lane and 64-element step: the authority for what
+          // the four-wide steps below leave alone — a scalar beyond ASCII (TB_WIDE), a style anchor, a control character that is
+          // written \u00XX
+          auto per_element = [&](uint32_t eb, uint32_t ee) {
             uint32_t cv[EU], gv[EU];
 #pragma unroll
             for (int u = 0; u < EU; u++) {
-              uint32_t e = e0 + 64u * (uint32_t)u + (uint32_t)lane;
+              uint32_t e = eb + 64u * (uint32_t)u + (uint32_t)lane;
               cv[u] = 0x20; gv[u] = 0;
-              if (e < total) {
+              if (e < ee) {
                 uint32_t lo = 0, hi = 63;                  // first run whose running length exceeds e
                 while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (s_inc[mid] > e) hi = mid; else lo = mid + 1; }
                 gv[u] = s_g0[lo] + e;                      // 32-bit wrap-around arithmetic: g0 may be "negative"
@@ -836,23 +846,111 @@ LM_DEV void emit_doc(Dev d, int mode, int pass) {
             }
 #pragma unroll
             for (int u = 0; u < EU; u++) {
-              uint32_t eu = e0 + 64u * (uint32_t)u;
-              if (eu >= total) break;
+              uint32_t eu = eb + 64u * (uint32_t)u;
+              if (eu >= ee) break;
               uint32_t e = eu + (uint32_t)lane, cpv = cv[u];
               // a step of plain ASCII (nothing to escape): scalar = byte, lane = output position — no scan, no byte loop
               if (!lmw::ballot(cpv < 0x20 || cpv >= 0x80 || cpv == '"' || cpv == '\\')) {
-                uint32_t cnt = total - eu < 64 ? total - eu : 64;
-                if (s.out && s.pos + cnt <= s.cap && e < total) s.out[s.pos + (uint32_t)lane] = (uint8_t)cpv;
+                uint32_t cnt = ee - eu < 64 ? ee - eu : 64;
+                if (s.out && s.pos + cnt <= s.cap && e < ee) s.out[s.pos + (uint32_t)lane] = (uint8_t)cpv;
                 s.pos += cnt;
               } else {
                 uint64_t bytes = 0;
                 uint32_t nb = 0;
-                if (e < total) {
+                if (e < ee) {
                   if (cpv == TB_WIDE) cpv = d.cp[elem0 + gv[u]]; else if (cpv == TB_ANCHOR) cpv = 0xFFFFFFFFu;
                   cp_bytes(cpv, bytes, nb);
                 }
                 sink_lanes(s, bytes, nb);
               }
+            }
+          };
+          // A step covers 256 elements, four consecutive ones per lane: ONE search per lane (its first position; the run index
+          // of the next three only moves forward), ONE unaligned 32-bit load when the four lie in one run.  The lane's bytes
+          // expand in registers (", \ and \b \t \n \f \r become two bytes), a scan of the lengths places them in the wave's LDS
+          // window, and the window leaves as aligned 16-byte pieces — the window is addressed from `s.pos & 15`, so piece i
+          // of the window is piece i of the slab (slabs start on multiples of 16, lm_pipeline.h).  The few bytes in front of
+          // the first and behind the last whole piece are written singly, by lanes 0-15 and 16-31.
+          // A step in which any lane holds another byte (>= 0x80: TB_WIDE / TB_ANCHOR; a control character without a short
+          // escape) is rendered by per_element instead.  The gathers of SU steps go out before the first is consumed.
+          #ifndef LM_EMIT_SU
+#define LM_EMIT_SU 2
+#endif
+          static constexpr int SU = LM_EMIT_SU;
+          static_assert(EU == 4, "per_element renders the 256 elements of one step");
+          LM_SHARED(EmitPiece, s_win, 33);            // 15 bytes of misalignment + 512 bytes of a step
+          uint8_t* const wb = (uint8_t*)s_win;
+          // (k_emit_any keeps the step of one element per lane: it has no registers left for the four-wide one)
+          if constexpr (!TEXT_ONLY) { for (uint32_t e0 = 0; e0 < total; e0 += 64 * EU) per_element(e0, total); }
+          else for (uint32_t e0 = 0; e0 < total; e0 += 256u * SU) {
+            uint32_t wv[SU] = {};
+#pragma unroll
+            for (int u = 0; u < SU; u++) {
+              if (e0 + 256u * (uint32_t)u >= total) break;
+              // (positions at or beyond `total` are clamped to the leaf's last element: every lane searches and loads without a
+              // predicate, and what it loaded there is not counted below)
+              const uint32_t e = e0 + 256u * (uint32_t)u + 4u * (uint32_t)lane, ec = e < total ? e : total - 1;
+              uint32_t lo = 0;                             // first run whose running length exceeds ec: six steps, no branch
+#pragma unroll
+              for (uint32_t st = 32; st; st >>= 1) if (s_inc[lo + st - 1] <= ec) lo += st;
+              if (e + 4 <= s_inc[lo]) wv[u] = ld32u(d.tb + elem0 + (uint32_t)(s_g0[lo] + e));   // all four in this run
+              else {
+                uint32_t gk[4];                            // the four loads go out together
+#pragma unroll
+                for (uint32_t k = 0; k < 4; k++) {
+                  const uint32_t ek = e + k < total ? e + k : total - 1;
+                  while (s_inc[lo] <= ek) lo++;            // (a loop: runs that show nothing repeat the running length; ek < total = s_inc[63] ends it)
+                  gk[k] = s_g0[lo] + ek;
+                }
+                const uint32_t b0 = d.tb[elem0 + gk[0]], b1 = d.tb[elem0 + gk[1]], b2 = d.tb[elem0 + gk[2]], b3 = d.tb[elem0 + gk[3]];
+                wv[u] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
+              }
+            }
+            uint32_t redo = NONE;
+#pragma unroll
+            for (int u = 0; u < SU; u++) {
+              const uint32_t eu = e0 + 256u * (uint32_t)u;
+              if (eu >= total) break;
+              const uint32_t e = eu + 4u * (uint32_t)lane;
+              const uint32_t nv = e < total ? (total - e < 4 ? total - e : 4u) : 0u;
+              uint64_t ob = 0;
+              uint32_t on = 0;
+              bool bad = false;
+#pragma unroll
+              for (uint32_t k = 0; k < 4; k++) {
+                const uint32_t c = (wv[u] >> (8 * k)) & 0xffu, t = c - 8u;
+                // second byte of the escape: the letter of \b \t \n . \f \r — 0x60 | five bits of a table, 0: none (\u00XX) —
+                // and the byte itself for " and backslash
+                const uint32_t code = t < 6 ? (0x24603a82u >> (5 * t)) & 31u : 0u;
+                const uint32_t sec = c < 0x20 ? (code ? 0x60u | code : 0u) : c;
+                const bool esc = c < 0x20 || c == '"' || c == '\\', in = k < nv;
+                bad |= in && (c >= 0x80 || sec == 0);
+                ob |= (uint64_t)(esc ? ((uint32_t)'\\' | (sec << 8)) : c) << (8 * on);   // (beyond nv: lands above the bytes that count)
+                on += in ? (esc ? 2u : 1u) : 0u;
+              }
+              if (lmw::any(bad)) { redo = eu; break; }
+              const uint32_t inc = lmw::scan_incl_add(on), tot = lmw::bcast(inc, 63);
+              if (s.out && s.pos + tot <= s.cap) {
+                const uint32_t a = (uint32_t)s.pos & 15u, at = a + inc - on, end = a + tot;
+                lmw::wave_sync();                          // (the previous step's pieces have been read)
+                if (on >= 4) st32u(wb + at, (uint32_t)ob);
+                else { if (on > 0) wb[at] = (uint8_t)ob; if (on > 1) wb[at + 1] = (uint8_t)(ob >> 8); if (on > 2) wb[at + 2] = (uint8_t)(ob >> 16); }
+#pragma unroll
+                for (uint32_t k = 4; k < 8; k++) if (k < on) wb[at + k] = (uint8_t)(ob >> (8 * k));
+                lmw::wave_sync();
+                uint8_t* const dst = s.out + (s.pos - a);  // where window byte 0 belongs: a multiple of 16 into the slab
+                const uint32_t l = (uint32_t)lane, p0 = 16u * l, jt = (end - 1) >> 4;
+                if (p0 >= a && p0 + 16 <= end) st128(dst + p0, s_win[l]);
+                const uint32_t idx = l < 16 ? l : 16u * jt + (l - 16);
+                const bool single = l < 16 ? ((a != 0 || end < 16) && idx >= a && idx < end)       // the first piece is not whole
+                                           : (l < 32 && jt != 0 && (end & 15u) != 0 && idx < end);  // nor is the last one
+                if (single) dst[idx] = wb[idx];
+              }
+              s.pos += tot;
+            }
+            if (redo != NONE) {
+              per_element(redo, total);
+              e0 = redo + 256u - 256u * SU;                // (wraps; the loop's increment lands behind the step just rendered)
             }
           }
         }
