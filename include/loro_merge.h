@@ -187,8 +187,11 @@ int lm_import(lm_ctx* ctx, const lm_doc_in* docs, size_t n_docs);
 /* What the reference computes before it diffs an import — the common ancestors of the version a document was at and the version
  * it reaches, and the DiffMode they imply (dag.rs:318-332,487-765 `find_common_ancestor`; oplog.rs:591-615; diff_calc.rs:72-103) —
  * computed on the device for every resident document by the last lm_run (one step = one import of all the step's blobs).
+ * The version a document "was at" is the one it held after its last step that went through: a step that fails leaves it
+ * there, so the step after a failed one is measured from the same version as the failed one was (the empty version if no
+ * step went through yet); a step whose checkout alone was refused (LM_FRONTIERS_NOT_FOUND) went through.
  * modes[i]: 0 Checkout, 1 Import, 2 ImportGreaterUpdates, 3 Linear, -1 unknown (no resident run, failed document, more than 16
- * common-ancestor ids).  lm_import_lca writes Frontiers::encode() of document `doc`'s common ancestors into buf (returns the
+ * common-ancestor ids, a version of more than 64 heads).  lm_import_lca writes Frontiers::encode() of document `doc`'s common ancestors into buf (returns the
  * length, -1 when unknown or cap is too small).  The engine itself does not branch on the mode — its trackers hold the whole
  * history, so the replay base is wherever the tracker stands — it reports what a host that mirrors the reference needs. */
 int lm_import_modes(lm_ctx* ctx, int32_t* modes);

@@ -383,6 +383,7 @@ struct lm_ctx_impl {
     for (uint32_t p = 0; p < np; p++) {
       lm::Engine& e = *parts[p];
       e.tables_valid = false; e.have_prev = false;
+      e.keep_ver.assign(e.n_docs, {}); e.keep_on.assign(e.n_docs, 0);   // (kept versions go wherever have_prev goes)
       std::fill(e.tk_reset.begin(), e.tk_reset.end(), (uint8_t)1);
       for (uint32_t i = 0; i < e.n_docs; i++) e.r_step[i] = (uint32_t)e.r_blobs[i].size();   // (a document whose import fails is empty afterwards, loro.rs:780-838)
       sh.out_top[p] = sh.vv_top[p] = 0;

@@ -1,6 +1,9 @@
 // The DAG query the reference asks before it diffs an import: the common ancestors of the version the document was at and the
 // version it reaches, and the DiffMode they imply.  One wave per resident document whose history grew; the walk
 // is a priority queue over spans of DAG nodes and is serial by nature — lane 0 runs it, on the tables k_dag_a / k_dag_b built.
+// "The version the document was at" (`from`) is the one it held after its last step that went through: the previous run's tables,
+// or — after a step that failed and was dropped again — the version the host kept for it (DevLca::keep_*); never the failed step's.
+// No answer (DM_UNKNOWN): a failed document, more than LCA_MAXF common ancestors, a version of more than LCA_FMAX heads.
 // Reference (paths relative to /root/reference/crates/loro-internal/src):
 //   find_common_ancestor / _find_common_ancestor_new        dag.rs:318-332, 487-765   (OrdIdSpan order :269-280, NodeType :282-287)
 //   deps of a span incl. the peer's previous op              dag.rs:592-608
@@ -25,6 +28,11 @@ struct DevLca {
   const DocMeta* prev_doc;       // nullptr: there was no previous run
   const uint64_t* prev_uniq;
   const uint32_t* prev_end;
+  // documents whose last step(s) failed: the version they were left at — the one after their last step that went through — kept
+  // by the host (Engine::keep_ver), since the previous run's tables describe the step that was dropped again
+  const uint32_t* keep_idx;      // nullptr: no such document; else [2 * doc] = first entry (NONE: not kept), [2 * doc + 1] = entries
+  const uint64_t* keep_uniq;     // PeerIDs, ascending per document
+  const uint32_t* keep_end;      // applied ends
 };
 
 struct LcaNode { uint32_t peer, ctr0, len, lam, dep0, n_dep; };
@@ -137,15 +145,20 @@ LM_KERNEL void k_import_lca(Dev d, DevDag g, DevLca lc) {
   uint32_t from[MAX_PEERS], to[MAX_PEERS];
   bool same = true, to_ge = true, to_gt = false;
   for (uint32_t p = 0; p < P; p++) { from[p] = 0; to[p] = d.peer_end_all[m.praw0 + p]; }
-  if (lc.prev_doc) {
+  // `from` is the version the document held after its last step that went through: the previous run's, unless that run failed
+  // for the document — then the kept one (a failed step leaves the document as it was, loro.rs:780-838); empty if there is none
+  auto from_peer = [&](uint64_t id, uint32_t end) {
+    uint32_t lo = 0, hi = P;
+    while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (d.peer_uniq[m.praw0 + mid] < id) lo = mid + 1; else hi = mid; }
+    if (lo < P && d.peer_uniq[m.praw0 + lo] == id) from[lo] = end;
+  };
+  if (lc.keep_idx && lc.keep_idx[2 * doc] != NONE) {
+    const uint32_t k0 = lc.keep_idx[2 * doc], kn = lc.keep_idx[2 * doc + 1];
+    for (uint32_t q = 0; q < kn; q++) from_peer(lc.keep_uniq[k0 + q], lc.keep_end[k0 + q]);
+  } else if (lc.prev_doc) {
     const DocMeta pm = lc.prev_doc[doc];
     if (!status_fatal(pm.status))
-      for (uint32_t q = 0; q < pm.n_peers; q++) {
-        uint64_t id = lc.prev_uniq[pm.praw0 + q];
-        uint32_t lo = 0, hi = P;
-        while (lo < hi) { uint32_t mid = (lo + hi) >> 1; if (d.peer_uniq[m.praw0 + mid] < id) lo = mid + 1; else hi = mid; }
-        if (lo < P && d.peer_uniq[m.praw0 + lo] == id) from[lo] = lc.prev_end[pm.praw0 + q];
-      }
+      for (uint32_t q = 0; q < pm.n_peers; q++) from_peer(lc.prev_uniq[pm.praw0 + q], lc.prev_end[pm.praw0 + q]);
   }
   for (uint32_t p = 0; p < P; p++) { same &= from[p] == to[p]; to_ge &= to[p] >= from[p]; to_gt |= to[p] > from[p]; if (from[p] > to[p]) from[p] = to[p]; }
   uint32_t lf_p[LCA_FMAX], lf_c[LCA_FMAX], rf_p[LCA_FMAX], rf_c[LCA_FMAX];

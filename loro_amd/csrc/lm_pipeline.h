@@ -172,6 +172,13 @@ struct Engine {
   DBuf b_elem_cap, b_old_blobs, b_prev_doc, b_prev_uniq, b_prev_end, b_lca_out, b_lca_scratch, b_lca_off;
   bool have_prev = false;                         // the tables of a previous resident run exist (what k_import_lca measures the import against)
   std::vector<uint32_t> h_lca;                    // per document LCA_OUT words of the last run: DiffMode + common ancestors of its import
+  // a document whose last step(s) failed: the version it was left at, (PeerID ascending, applied end) — taken from the b_prev_*
+  // copies when the first of those steps fails, dropped by its next step that goes through.  k_import_lca measures such a
+  // document from here: the previous run's tables describe the step that was dropped again.
+  std::vector<std::vector<std::pair<uint64_t, uint32_t>>> keep_ver;
+  std::vector<uint8_t> keep_on;
+  bool prev_copied = false;                       // this run took the b_prev_* copies
+  DBuf b_keep_idx, b_keep_uniq, b_keep_end;
   std::vector<uint8_t> tk_reset;
   void upload_res() {   // the per-document records of this run (tracker record, capacities, reset flag)
     std::vector<ResDoc> hres(n_docs);
@@ -315,7 +322,7 @@ struct Engine {
                    &b_node_last, &b_node_order, &b_vvh, &b_blk_sorted, &b_chg_node, &b_node_done, &b_node_lam, &b_cp, &b_loc, &b_kept, &b_tb, &b_it,
                    &b_dir_out, &b_lf_chunk, &b_fuse, &b_dcnt, &b_posdel, &b_pd_off, &b_pd_row,
                    &b_cont_root0, &b_cont_nroot, &b_prof, &b_hash, &b_order, &b_ht_key, &b_ht_pfx, &b_ht_best, &b_ht0, &b_ht_cap, &b_ht_list, &b_ht_cnt, &b_slab, &b_vslab, &b_slab_off, &b_vslab_off, &b_slab2, &b_slab2_off, &b_out, &b_out_off,
-                   &b_vv_out, &b_vv_off, &b_tk, &b_res, &b_dir_out2, &b_dir_b, &b_dir_b2, &b_doc_saved, &b_elem_cap, &b_old_blobs, &b_prev_doc, &b_prev_uniq, &b_prev_end, &b_lca_out, &b_lca_scratch, &b_lca_off};
+                   &b_vv_out, &b_vv_off, &b_tk, &b_res, &b_dir_out2, &b_dir_b, &b_dir_b2, &b_doc_saved, &b_elem_cap, &b_old_blobs, &b_prev_doc, &b_prev_uniq, &b_prev_end, &b_lca_out, &b_lca_scratch, &b_lca_off, &b_keep_idx, &b_keep_uniq, &b_keep_end};
     for (DBuf* b : all) b->release();
     for (DBuf* b : {&b_dl_q, &b_dl_bnd, &b_dl_bits, &b_dl_res, &b_dl_out, &b_dl_off, &b_dl_pack, &b_dl_poff}) b->release();
   }
@@ -628,6 +635,7 @@ struct Engine {
     tk_elem0.assign(n_docs, 0); tk_elem_cap.assign(n_docs, 0); elem_top = 0;
     tk_top = 0; leaf_top = 0; dir_parity = 0;
     resident = true; tables_valid = false; have_prev = false;
+    keep_ver.assign(n_docs, {}); keep_on.assign(n_docs, 0);
   }
   // The resident batch becomes a batch of src.size() documents, document i holding the blobs of the present document src[i] — the
   // SAME bytes of the arena — and rendered at fronts[i] by the next run: what lm_import needs from a batch that was staged folded
@@ -659,6 +667,7 @@ struct Engine {
     tk_top = 0; leaf_top = 0; dir_parity = 0;
     tk_new.clear();
     tables_valid = false; have_prev = false; h_lca.clear();
+    keep_ver.assign(n_docs, {}); keep_on.assign(n_docs, 0);
     shared_mode = 0;
     rebuild_blob_tables();
     lmbe::sync();
@@ -743,8 +752,10 @@ struct Engine {
       // then form the documents' first step together — one import_batch.)
       const bool was_run = ran;
       adopt_resident();
+      // the staged blobs are the first step (alone, or together with what this call brings): a document whose first import fails
+      // is empty again afterwards (loro.rs:780-838) — also when no lm_run came in between
+      for (uint32_t i = 0; i < n_docs; i++) r_step[i] = (uint32_t)r_blobs[i].size();
       if (was_run && n_blobs) {
-        for (uint32_t i = 0; i < n_docs; i++) r_step[i] = (uint32_t)r_blobs[i].size();   // a document whose batch import failed is empty again afterwards (loro.rs:780-838)
         run();
         lmbe::bind(sc);
       }
@@ -850,9 +861,11 @@ struct Engine {
     // resident documents whose blob lists did not change since the tables were built: only the rendered versions differ —
     // the decode / DAG stages are skipped, the saved tables are rendered again (k_dag_b's checkout part onwards)
     const bool reuse = resident && tables_valid;
+    prev_copied = resident && have_prev;
     if (resident && have_prev) {
       // the version every document was at before this run (k_import_lca: LCA + DiffMode of the import, dag.rs:487-765): the
-      // previous run's document records, peers and applied ends, copied before this run's kernels rebuild the tables
+      // previous run's document records, peers and applied ends, copied before this run's kernels rebuild the tables.  For a
+      // document that run FAILED for, these describe the step that was dropped again: its version is keep_ver's (below)
       b_prev_doc.ensure((size_t)n_docs * sizeof(DocMeta)); lmbe::d2d(b_prev_doc.p, b_doc_saved.p, (size_t)n_docs * sizeof(DocMeta));
       b_prev_uniq.ensure((size_t)(sv.NP + 1) * 8); lmbe::d2d(b_prev_uniq.p, b_peer_uniq.p, (size_t)(sv.NP + 1) * 8);
       b_prev_end.ensure((size_t)(sv.NP + 1) * 4); lmbe::d2d(b_prev_end.p, b_peer_end_all.p, (size_t)(sv.NP + 1) * 4);
@@ -1276,6 +1289,22 @@ struct Engine {
       DevLca lc;
       lc.out = b_lca_out.as<uint32_t>(); lc.scratch = b_lca_scratch.as<uint32_t>(); lc.scratch_off = b_lca_off.as<uint64_t>();
       lc.prev_doc = have_prev ? b_prev_doc.as<DocMeta>() : nullptr; lc.prev_uniq = b_prev_uniq.as<uint64_t>(); lc.prev_end = b_prev_end.as<uint32_t>();
+      lc.keep_idx = nullptr; lc.keep_uniq = nullptr; lc.keep_end = nullptr;
+      bool any_keep = false;
+      for (uint32_t i = 0; i < n_docs && !any_keep; i++) any_keep = i < keep_on.size() && keep_on[i];
+      if (any_keep) {   // documents left at an earlier version by failed steps: measured from that version
+        std::vector<uint32_t> kidx((size_t)n_docs * 2, NONE), kend;
+        std::vector<uint64_t> kuniq;
+        for (uint32_t i = 0; i < n_docs; i++) {
+          if (!keep_on[i]) continue;
+          kidx[2 * i] = (uint32_t)kuniq.size(); kidx[2 * i + 1] = (uint32_t)keep_ver[i].size();
+          for (const auto& pe : keep_ver[i]) { kuniq.push_back(pe.first); kend.push_back(pe.second); }
+        }
+        b_keep_idx.ensure(kidx.size() * 4); lmbe::h2d(b_keep_idx.p, kidx.data(), kidx.size() * 4);
+        b_keep_uniq.ensure(kuniq.size() * 8 + 8); if (!kuniq.empty()) lmbe::h2d(b_keep_uniq.p, kuniq.data(), kuniq.size() * 8);
+        b_keep_end.ensure(kend.size() * 4 + 4); if (!kend.empty()) lmbe::h2d(b_keep_end.p, kend.data(), kend.size() * 4);
+        lc.keep_idx = b_keep_idx.as<uint32_t>(); lc.keep_uniq = b_keep_uniq.as<uint64_t>(); lc.keep_end = b_keep_end.as<uint32_t>();
+      }
       lmbe::tic(profiling);
       LM_LAUNCH(k_import_lca, n_docs, 64, d, g, lc);
       lmbe::toc("k_import_lca", times, profiling);
@@ -1622,7 +1651,22 @@ struct Engine {
         if (h_doc[i].status != ST_OK) {
           if (r_step[i]) { r_blobs[i].resize(r_blobs[i].size() - r_step[i]); dropped = true; }
           tk_reset[i] = 1;
-        } else tk_reset[i] = 0;
+          // … and the version it stays at is kept for k_import_lca: what the previous run left (this run's copy of it), or
+          // what is kept already when that run had failed too; nothing (the empty version) when no run went through yet
+          if (!keep_on[i]) {
+            keep_on[i] = 1; keep_ver[i].clear();
+            DocMeta pm;
+            if (prev_copied) {
+              lmbe::d2h(&pm, (const uint8_t*)b_prev_doc.p + (size_t)i * sizeof(DocMeta), sizeof(DocMeta));
+              if (pm.status == ST_OK && pm.n_peers) {
+                std::vector<uint64_t> ids(pm.n_peers); std::vector<uint32_t> ends(pm.n_peers);
+                lmbe::d2h(ids.data(), b_prev_uniq.as<uint64_t>() + pm.praw0, (size_t)pm.n_peers * 8);
+                lmbe::d2h(ends.data(), b_prev_end.as<uint32_t>() + pm.praw0, (size_t)pm.n_peers * 4);
+                for (uint32_t q = 0; q < pm.n_peers; q++) if (ends[q]) keep_ver[i].push_back({ids[q], ends[q]});
+              }
+            }
+          }
+        } else { tk_reset[i] = 0; keep_on[i] = 0; }
         r_step[i] = 0;
       }
       h_lca.resize((size_t)n_docs * LCA_OUT);
