@@ -518,7 +518,11 @@ struct lm_ctx_impl {
     if (at == d0 || at >= body_end || k[at] != '@' || ctr > (1ull << 31)) return;
     at++;
     d0 = at;
-    while (at < body_end && k[at] >= '0' && k[at] <= '9') { if (peer > (~0ull - 9) / 10) return; peer = peer * 10 + (k[at++] - '0'); }
+    while (at < body_end && k[at] >= '0' && k[at] <= '9') {     // (up to 2^64 - 1 itself: the bound is the digit's, not 9's)
+      const uint64_t dg = (uint64_t)(k[at++] - '0');
+      if (peer > (~0ull - dg) / 10) return;
+      peer = peer * 10 + dg;
+    }
     if (at == d0 || at != body_end) return;
     q.kind_root = kind; q.cpeer = peer; q.ccounter = (uint32_t)(neg ? -(int64_t)ctr : (int64_t)ctr); q.ok = true;
   }
