@@ -353,6 +353,69 @@ typedef struct lm_cursor_at_result {
 int lm_cursor_pos(lm_ctx* ctx, const lm_cursor_query* queries, size_t n, lm_cursor_result* out);
 int lm_cursor_at(lm_ctx* ctx, const lm_cursor_at_query* queries, size_t n, lm_cursor_at_result* out);
 
+/* ---- Frontiers and version vectors.  lm_fetch hands out a VersionVector and lm_delta* / lm_export take one; checkout_frontiers,
+ * LoroDoc::diff / checkout / cmp_frontiers and every event of the reference speak Frontiers.  A host that offloads its imports holds
+ * no DAG of its own; these two calls answer from the one the last lm_run left on the device (k_version, loro_amd/csrc/lm_k_version.h).
+ *
+ * lm_frontiers: the heads of document `doc` after the last lm_run as Frontiers::encode() bytes (postcard Vec<ID>, sorted), with
+ * lm_import_lca's buffer convention: returns the length, -1 (lm_last_error) when there is none — before lm_run, a run in flight, a
+ * document index beyond the batch, a document that failed in a batch run or has no rendering — or when `cap` is too small.
+ *   which = 0: oplog_frontiers (loro.rs:1377) — the heads of everything APPLIED, whatever version was rendered;
+ *   which = 1: state_frontiers (loro.rs:1382) — the heads of the version that run RENDERED (== which 0 without a checkout; a resident
+ *              document whose checkout was refused stands at its latest version).
+ * Computed for all documents by one launch behind the first call after a run and kept until the next run.
+ *
+ * lm_versions: n queries in one launch, one wave each.  Every operation is evaluated over the APPLIED history of the document, not
+ * over the rendered version (the reference asks its oplog's DAG: a checked-out document still converts versions beyond its
+ * checkout); pending changes are not part of that history.  By id sets: closure(id) = the id and its causal past, closure(F) = the
+ * union over F, heads(S) = the ids of S that no other id of S has in its past.
+ *   LM_VER_TO_VV (loro_dag.rs:1192-1207)         a = Frontiers; bytes = VersionVector::encode() of closure(a).  00 is the empty
+ *       version and gives the empty vector; two ids of one peer are both taken (the greater decides).  The bytes are what lm_fetch
+ *       returns as `vv` when that version is checked out: pass them as from_vv to lm_delta* / lm_export as they are.
+ *   LM_VER_TO_FRONTIERS (loro_dag.rs:1269-1298)  a = VersionVector; bytes = Frontiers::encode() of heads({(p, a[p] - 1) : a[p] > 0}).
+ *       Entries of 0 (or below) are skipped.  The vector need not be causally closed: this is the shrink of its last ids.
+ *   LM_VER_MINIMIZE (lib.rs:855)                 a = Frontiers; bytes = Frontiers::encode() of heads(a).
+ *   LM_VER_CMP (loro_dag.rs:1347-1355)           a, b = Frontiers; order = -1 / 0 / 1 for closure(a) a proper subset of / equal to /
+ *       a proper superset of closure(b), 2 when neither contains the other.
+ *   LM_VER_CMP_DOC (loro_dag.rs:1333-1341)       a = Frontiers; order = 0 when a equals the document's oplog frontiers as a set of
+ *       ids; else 1 when the applied vector includes every id of a (a vector test, no DAG lookup); else -1 ("less or parallel": an
+ *       unknown id lands here and is no error).
+ * Statuses: LM_FRONTIERS_NOT_FOUND (all but CMP_DOC) — an id outside the applied history: an unknown peer, a counter at or beyond the
+ * peer's applied end, a negative counter, an id inside a pending change; for TO_FRONTIERS an entry above 0 of an unknown peer or beyond
+ * the applied end.  LM_DECODE_ERROR — bytes that are not a Frontiers / a VersionVector (truncated, bytes left over, zero length: the
+ * empty version is the byte 00).  The document's own import error for a failed document, LM_UNSUPPORTED for one without a rendering
+ * (an engine limit, a shallow snapshot); a document that only carries Tree / Counter containers beside the rest answers normally.
+ * Returns 0, or -1 (lm_last_error) before lm_run, during a run in flight, for a document index beyond the batch or an op outside the
+ * enum.  Batch shapes: a document staged from a snapshot's STATE section is staged once more through its history and run again; a
+ * batch folded by shared replay is UNFOLDED by the first call (which = 1 needs every entry's own rendered version; every entry then
+ * holds the one applied history, so which = 0 and lm_versions answer alike for the entries of one document); documents replayed in
+ * the side engine are answered there; resident documents answer for the state after the last lm_import + lm_run.
+ * After a FAILED step a resident document stands where it stood before, and so do its heads: lm_frontiers gives, both ways, what
+ * it gave after the document's last step that went through (the byte 00 when none did yet), unchanged until a step goes through
+ * and moves them on.  (Kept from the tables of the run before: a run that brings new blobs computes the heads in front of its
+ * decode stage unless a call already has; a run that only moves the rendered versions pays nothing, and a document such a run
+ * fails for has no heads: -1.)  lm_versions has no tables for that document — the failed run built none — and answers the step's
+ * error for it until a step goes through.
+ * The calls change nothing a run wrote: lm_fetch, lm_result_meta and lm_import_modes give the same bytes afterwards.
+ * LoroDoc::diff(a, b): check out b, LM_VER_TO_VV(a), lm_delta* (INTEGRATION.md). */
+long lm_frontiers(lm_ctx* ctx, size_t doc, int which, uint8_t* buf, size_t cap);
+enum { LM_VER_TO_VV = 0, LM_VER_TO_FRONTIERS = 1, LM_VER_MINIMIZE = 2, LM_VER_CMP = 3, LM_VER_CMP_DOC = 4 };
+typedef struct lm_version_query {
+  size_t doc;               /* index into the batch staged last */
+  int32_t op;               /* LM_VER_* */
+  const uint8_t* a;         /* Frontiers::encode() bytes; LM_VER_TO_FRONTIERS: VersionVector::encode() bytes */
+  size_t a_len;
+  const uint8_t* b;         /* LM_VER_CMP: the second Frontiers; unused otherwise */
+  size_t b_len;
+} lm_version_query;
+typedef struct lm_version_result {
+  int32_t status;           /* LM_OK | LM_FRONTIERS_NOT_FOUND | LM_DECODE_ERROR | the document's import error | LM_UNSUPPORTED */
+  int32_t order;            /* LM_VER_CMP: -1 / 0 / 1 / 2; LM_VER_CMP_DOC: -1 / 0 / 1; 0 otherwise */
+  const uint8_t* bytes;     /* TO_VV / TO_FRONTIERS / MINIMIZE; valid until the next lm_versions / lm_stage / lm_destroy */
+  size_t len;
+} lm_version_result;
+int lm_versions(lm_ctx* ctx, const lm_version_query* queries, size_t n, lm_version_result* out);
+
 /* ---- Text and List deltas between two versions: what changed since the version this subscriber has?  LoroDoc::diff(a, b) and the
  * TextDelta / ListDiffItem events of subscribe, answered on the device from the trackers and the decoded op rows the run left
  * (k_delta_mark, k_delta: loro_amd/csrc/lm_k_delta.h) instead of a fetch of the whole JSON and a string diff on the host — which

@@ -45,12 +45,22 @@ class DeltaResult(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("other_changed", ctypes.c_uint32), ("json", ctypes.c_void_p), ("json_len", ctypes.c_size_t)]
 
 
+class VersionQuery(ctypes.Structure):
+    _fields_ = [("doc", ctypes.c_size_t), ("op", ctypes.c_int32), ("a", ctypes.c_char_p), ("a_len", ctypes.c_size_t), ("b", ctypes.c_char_p), ("b_len", ctypes.c_size_t)]
+
+
+class VersionResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("order", ctypes.c_int32), ("bytes", ctypes.c_void_p), ("len", ctypes.c_size_t)]
+
+
+VER_TO_VV, VER_TO_FRONTIERS, VER_MINIMIZE, VER_CMP, VER_CMP_DOC = range(5)
 CURSOR_OK, CURSOR_DELETED, CURSOR_ID_NOT_FOUND, CURSOR_CONTAINER_NOT_FOUND, CURSOR_DOC_FAILED, CURSOR_UNSUPPORTED = range(6)
 
 SYMBOLS = ["create", "destroy", "last_error", "merge_batch", "stage", "run", "fetch", "get_stats", "set_profiling", "kernel_time", "selftest", "result_meta", "result_hashes", "n_streams", "run_async", "wait",
            "encode_block", "encode_updates", "free_bytes", "import", "resident_fresh", "import_modes", "import_lca", "export", "comm_unique_id", "comm_init", "summary_allgather",
            "summary_layout", "summary_rows_device", "summary_allgather_device", "shared_documents", "richtext", "richtext_result", "fused_documents", "redo_documents", "state_documents", "host_alloc", "host_free", "staged_direct",
-           "cursor_pos", "cursor_at", "delta", "delta_bytes", "delta_map", "delta_movable", "delta_richtext"]
+           "cursor_pos", "cursor_at", "delta", "delta_bytes", "delta_map", "delta_movable", "delta_richtext",
+           "frontiers", "versions"]
 
 
 class Binding:
@@ -91,6 +101,10 @@ class Binding:
         self.cursor_pos.argtypes = [ctypes.c_void_p, ctypes.POINTER(CursorQuery), ctypes.c_size_t, ctypes.POINTER(CursorResult)]
         self.cursor_at = g("cursor_at"); self.cursor_at.restype = ctypes.c_int
         self.cursor_at.argtypes = [ctypes.c_void_p, ctypes.POINTER(CursorAtQuery), ctypes.c_size_t, ctypes.POINTER(CursorAtResult)]
+        self.frontiers = g("frontiers"); self.frontiers.restype = ctypes.c_long
+        self.frontiers.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+        self.versions = g("versions"); self.versions.restype = ctypes.c_int
+        self.versions.argtypes = [ctypes.c_void_p, ctypes.POINTER(VersionQuery), ctypes.c_size_t, ctypes.POINTER(VersionResult)]
         self.delta = g("delta"); self.delta.restype = ctypes.c_int
         self.delta.argtypes = [ctypes.c_void_p, ctypes.POINTER(DeltaQuery), ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(DeltaResult)]
         self.delta_map = g("delta_map"); self.delta_map.restype = ctypes.c_int
@@ -313,6 +327,28 @@ class Context:
         if self.b.cursor_at(self.h, qs, n, out) != 0:
             raise RuntimeError(self.b.last_error(self.h).decode())
         return [(out[k].status, (out[k].peer, out[k].counter) if out[k].has_id else None, out[k].side, out[k].origin_pos) for k in range(n)]
+
+    def frontiers(self, doc, which=0):
+        """lm_frontiers: the heads of document `doc` after the last run as Frontiers::encode() bytes — which 0: of everything applied
+        (oplog_frontiers), 1: of the version the run rendered (state_frontiers).  None when the document has none (it failed)."""
+        buf = ctypes.create_string_buffer(16 * 256 + 16)
+        n = self.b.frontiers(self.h, doc, which, buf, len(buf))
+        return buf.raw[:n] if n >= 0 else None
+
+    def versions(self, queries):
+        """lm_versions: Frontiers <-> VersionVector, heads and comparisons over the applied history of the last run's documents.
+        queries: [(doc, op, a)] or [(doc, op, a, b)] — op = VER_*, a / b = encoded Frontiers (VER_TO_FRONTIERS: a = encoded
+        VersionVector).  Returns [(status, order, bytes)]."""
+        n = len(queries)
+        qs, out, keep = (VersionQuery * max(n, 1))(), (VersionResult * max(n, 1))(), []
+        for k, q in enumerate(queries):
+            a = None if q[2] is None else bytes(q[2])
+            b = None if len(q) < 4 or q[3] is None else bytes(q[3])
+            keep.append((a, b))
+            qs[k].doc = q[0]; qs[k].op = q[1]; qs[k].a = a; qs[k].a_len = len(a) if a else 0; qs[k].b = b; qs[k].b_len = len(b) if b else 0
+        if self.b.versions(self.h, qs, n, out) != 0:
+            raise RuntimeError(self.b.last_error(self.h).decode())
+        return [(out[k].status, out[k].order, ctypes.string_at(out[k].bytes, out[k].len) if out[k].len else b"") for k in range(n)]
 
     def _delta(self, call, queries, *units):
         n = len(queries)

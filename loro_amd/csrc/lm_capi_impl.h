@@ -296,6 +296,7 @@ struct lm_ctx_impl {
     sum_rows_padded = 0;             // (a new batch: lm_summary_layout is called again for it)
     for (auto& pt : parts) { pt->sum_rows = nullptr; pt->keep_tombstones = false; pt->no_map_fused = false; }
     dl_json.clear();
+    ver_bytes.clear();
     // split into contiguous ranges of about equal blob bytes; small batches stay in one part
     uint64_t total = 0;
     for (size_t i = 0; i < n; i++) for (size_t b = 0; b < docs[i].n; b++) total += docs[i].lens[b];
@@ -565,6 +566,88 @@ struct lm_ctx_impl {
       for (size_t j = 0; j < of[p].size(); j++) out[of[p][j]] = r[j];
       if (profiling) times.push_back(lm::KernelTime{"k_cursor", e.cur_ms});
     }
+  }
+
+  // ---- lm_frontiers / lm_versions (lm_k_version.h).  The batch shapes are the cursor calls', minus the replay that keeps tombstones
+  // (nothing here reads a tracker): a document staged from a snapshot's STATE has no DAG below its base version (staged once more
+  // through its history), a folded batch is unfolded — which = 1 needs every entry's rendered version, and the entries' resident
+  // documents all hold the one applied history that which = 0 and lm_versions answer from — documents replayed in the side engine are
+  // answered there.  lm_fetch / lm_result_meta give the same bytes afterwards.
+  std::vector<std::vector<uint8_t>> ver_bytes;   // the bytes of the last lm_versions' results: valid until the next lm_versions / lm_stage / lm_destroy
+  void version_prepare(const char* who) {
+    if (!ran) throw std::runtime_error(std::string(who) + " before lm_run");
+    if (in_flight) throw std::runtime_error(std::string(who) + " while a run is in flight");
+    bool any = false;
+    for (uint32_t p = 0; p < n_parts(); p++) if (parts[p]->n_state_docs && !parts[p]->resident) { parts[p]->restage_history(); any = true; }
+    if (any) { run(); sum_host_rows(); }
+    if (sh.on) { unfold(); ran = true; sum_host_rows(); }
+  }
+  // API document -> its engine and its index there
+  lm::Engine& version_engine(size_t doc, uint32_t& local) {
+    if (redone(doc)) { local = (uint32_t)rd.of[doc]; return *rd.eng; }
+    uint32_t p = 0;
+    if (mapped) { p = emap[doc].first; local = emap[doc].second; }
+    else { while (p + 1 < n_parts() && doc >= first[p + 1]) p++; local = (uint32_t)(doc - first[p]); }
+    return *parts[p];
+  }
+  // in[k].doc = API document; out[k] answers in[k]
+  void versions(std::vector<lm::Engine::VersionIn>& in, std::vector<lm::Engine::VersionOut>& out) {
+    version_prepare("lm_versions");
+    out.assign(in.size(), lm::Engine::VersionOut());
+    std::map<lm::Engine*, std::vector<uint32_t>> of;   // the queries of every engine
+    for (size_t k = 0; k < in.size(); k++) {
+      if (in[k].doc >= api_docs()) throw std::runtime_error("lm_versions: no such document");
+      uint32_t local = 0;
+      lm::Engine& e = version_engine(in[k].doc, local);
+      in[k].doc = local;
+      of[&e].push_back((uint32_t)k);
+    }
+    std::vector<lm::Engine::VersionIn> sub;
+    std::vector<lm::Engine::VersionOut> r;
+    for (auto& kv : of) {
+      lm::Engine& e = *kv.first;
+      e.profiling = profiling != 0;
+      sub.clear();
+      for (uint32_t k : kv.second) sub.push_back(in[k]);
+      e.versions(sub, r);
+      for (size_t j = 0; j < kv.second.size(); j++) out[kv.second[j]] = std::move(r[j]);
+      if (profiling) times.push_back(lm::KernelTime{"k_version", e.ver_ms});
+    }
+  }
+  bool frontiers(size_t doc, int which, std::vector<uint8_t>& out) {
+    version_prepare("lm_frontiers");
+    if (doc >= api_docs()) throw std::runtime_error("lm_frontiers: no such document");
+    uint32_t local = 0;
+    lm::Engine& e = version_engine(doc, local);
+    return e.frontiers(local, which, out);
+  }
+  // Frontiers::encode() / VersionVector::encode() (postcard: n, then PeerID u64 / counter i32 as LEB128, the counter zigzag) -> rows;
+  // false when the bytes are not one (truncated, a counter beyond 32 bits, bytes left over).  A VersionVector gives the last id of
+  // every entry above 0 (entries of 0 or below name no id: skipped, as lm_delta skips them)
+  static bool version_parse(const uint8_t* p, size_t n, bool vv, std::vector<std::pair<uint64_t, int64_t>>& rows) {
+    rows.clear();
+    if (!p || !n) return false;
+    size_t at = 0;
+    auto uleb = [&](uint64_t& v) -> bool {
+      v = 0;
+      for (uint32_t sh = 0; sh < 70; sh += 7) {
+        if (at >= n) return false;
+        const uint8_t x = p[at++];
+        if (sh == 63 && x > 1) return false;
+        v |= (uint64_t)(x & 0x7f) << sh;
+        if (x < 0x80) return true;
+      }
+      return false;
+    };
+    uint64_t cnt, peer, z;
+    if (!uleb(cnt) || cnt > n) return false;
+    for (uint64_t i = 0; i < cnt; i++) {
+      if (!uleb(peer) || !uleb(z) || z > 0xFFFFFFFFull) return false;
+      const int64_t c = (int64_t)(z >> 1) ^ -(int64_t)(z & 1);
+      if (!vv) rows.emplace_back(peer, c);
+      else if (c > 0) rows.emplace_back(peer, c - 1);
+    }
+    return at == n;
   }
 
   // ---- lm_delta (lm_k_delta.h): the batch shapes are the cursor calls' (cursor_prepare); the queries are routed to the engines
@@ -977,6 +1060,51 @@ int LM_API(cursor_at)(void* c, const lm_cursor_at_query_c* qs, size_t n, lm_curs
       if (r[k].len == 0) { o.side = qs[k].side == 0 ? -1 : qs[k].side; }
       else if (!r[k].has) { o.side = 1; o.origin_pos = r[k].len; }
       else { o.has_id = 1; o.peer = r[k].peer; o.counter = (int32_t)r[k].ctr; o.origin_pos = qs[k].pos; }
+    }
+    return 0;
+  } catch (const std::exception& e) { x->err = e.what(); return -1; }
+}
+// ---- Frontiers and version vectors (include/loro_merge.h): on the device, from the DAG tables of the last lm_run (lm_k_version.h)
+typedef struct lm_version_query_c { size_t doc; int32_t op; const uint8_t* a; size_t a_len; const uint8_t* b; size_t b_len; } lm_version_query_c;
+typedef struct lm_version_result_c { int32_t status; int32_t order; const uint8_t* bytes; size_t len; } lm_version_result_c;
+long LM_API(frontiers)(void* c, size_t doc, int which, uint8_t* buf, size_t cap) {
+  auto* x = (lm_ctx_impl*)c;
+  try {
+    if (which < 0 || which > 1) throw std::runtime_error("lm_frontiers: which is 0 (oplog_frontiers) or 1 (state_frontiers)");
+    std::vector<uint8_t> b;
+    if (!x->frontiers(doc, which, b)) { x->err = "lm_frontiers: the document has no version (it failed, or has no rendering)"; return -1; }
+    if (b.size() > cap) { x->err = "lm_frontiers: the buffer is too small"; return -1; }
+    memcpy(buf, b.data(), b.size());
+    return (long)b.size();
+  } catch (const std::exception& e) { x->err = e.what(); return -1; }
+}
+int LM_API(versions)(void* c, const lm_version_query_c* qs, size_t n, lm_version_result_c* out) {
+  auto* x = (lm_ctx_impl*)c;
+  try {
+    std::vector<lm::Engine::VersionIn> in;
+    std::vector<uint32_t> idx;               // in[j] answers query idx[j]; the others are LM_DECODE_ERROR
+    std::vector<int32_t> early(n, lm::ST_OK);
+    for (size_t k = 0; k < n; k++) {
+      if (qs[k].doc >= x->api_docs()) throw std::runtime_error("lm_versions: no such document");
+      if (qs[k].op < lm::VER_TO_VV || qs[k].op > lm::VER_CMP_DOC) throw std::runtime_error("lm_versions: op is one of LM_VER_*");
+      lm::Engine::VersionIn q;
+      q.doc = (uint32_t)qs[k].doc; q.op = qs[k].op;
+      bool ok = lm_ctx_impl::version_parse(qs[k].a, qs[k].a_len, qs[k].op == lm::VER_TO_FRONTIERS, q.a);
+      if (ok && qs[k].op == lm::VER_CMP) ok = lm_ctx_impl::version_parse(qs[k].b, qs[k].b_len, false, q.b);
+      if (!ok) { early[k] = lm::ST_DECODE_ERROR; q.a.clear(); q.b.clear(); q.op = lm::VER_TO_VV; }   // (still routed: a failed document answers with its own error)
+      if (q.op == lm::VER_CMP_DOC) { std::sort(q.a.begin(), q.a.end()); q.a.erase(std::unique(q.a.begin(), q.a.end()), q.a.end()); }   // a set of ids
+      in.push_back(std::move(q));
+    }
+    std::vector<lm::Engine::VersionOut> r;
+    x->versions(in, r);
+    x->ver_bytes.resize(n);
+    for (size_t k = 0; k < n; k++) {
+      const bool doc_ok = r[k].status == lm::ST_OK || r[k].status == lm::ST_FRONTIERS_NOT_FOUND;
+      if (early[k] != lm::ST_OK && doc_ok) { r[k].status = early[k]; r[k].order = 0; r[k].bytes.clear(); }
+      x->ver_bytes[k].swap(r[k].bytes);
+      x->ver_bytes[k].push_back(0);   // (never an empty vector: bytes is a valid pointer for every query)
+      out[k].status = r[k].status; out[k].order = r[k].order;
+      out[k].bytes = x->ver_bytes[k].data(); out[k].len = x->ver_bytes[k].size() - 1;
     }
     return 0;
   } catch (const std::exception& e) { x->err = e.what(); return -1; }

@@ -26,6 +26,7 @@
 #include "lm_k_lca.h"
 #include "lm_k_richtext.h"
 #include "lm_k_cursor.h"
+#include "lm_k_version.h"
 #include "lm_k_delta.h"
 #include "lm_k_delta_map.h"
 #include "lm_k_delta_movable.h"
@@ -137,6 +138,18 @@ struct Engine {
   bool no_map_fused = false;                      // the next runs decode every LWW Map document through the row tables (lm_delta_map needs its op rows)
   bool keep_tombstones = false;                   // the next runs replay without the linear prefix (it drops what it deletes from the leaves: cursor_needs_tombstones)
   double cur_ms = 0;                              // k_cursor of the last call (profiling)
+  // lm_frontiers / lm_versions (lm_k_version.h)
+  DevDag last_g;                                  // the DAG stage's tables of the last run, beside last_d
+  DBuf b_ver_q, b_ver_rows, b_ver_res, b_ver_out;
+  std::vector<uint64_t> h_ver_peers;              // the peer tables of the last run (b_peer_uniq), fetched by the first call behind it
+  bool ver_peers_ok = false;
+  std::vector<std::vector<uint8_t>> h_heads[2];   // lm_frontiers: per document Frontiers::encode() of the applied / the rendered version, by the first call behind a run
+  bool heads_ok = false;
+  // … and across a step that FAILED for a resident document: the document stands where it stood (keep_ver), and so do its heads —
+  // the bytes of the run before, taken when the first of those steps fails, dropped by the next step that goes through
+  std::vector<std::vector<uint8_t>> heads_kept[2];
+  std::vector<uint8_t> heads_kept_on;
+  double ver_ms = 0;                              // k_version of the last call (profiling)
   // lm_delta (lm_k_delta.h)
   DBuf b_dl_q, b_dl_bnd, b_dl_bits, b_dl_res, b_dl_out, b_dl_off, b_dl_pack, b_dl_poff;
   uint64_t dl_d2h_bytes = 0;                      // bytes the last lm_delta copied back (result rows + the packed JSON)
@@ -325,6 +338,7 @@ struct Engine {
                    &b_vv_out, &b_vv_off, &b_tk, &b_res, &b_dir_out2, &b_dir_b, &b_dir_b2, &b_doc_saved, &b_elem_cap, &b_old_blobs, &b_prev_doc, &b_prev_uniq, &b_prev_end, &b_lca_out, &b_lca_scratch, &b_lca_off, &b_keep_idx, &b_keep_uniq, &b_keep_end};
     for (DBuf* b : all) b->release();
     for (DBuf* b : {&b_dl_q, &b_dl_bnd, &b_dl_bits, &b_dl_res, &b_dl_out, &b_dl_off, &b_dl_pack, &b_dl_poff}) b->release();
+    for (DBuf* b : {&b_ver_q, &b_ver_rows, &b_ver_res, &b_ver_out}) b->release();
   }
 
   // ---- stage: pack the blobs (16-byte aligned starts) and upload
@@ -862,6 +876,17 @@ struct Engine {
     // the decode / DAG stages are skipped, the saved tables are rendered again (k_dag_b's checkout part onwards)
     const bool reuse = resident && tables_valid;
     prev_copied = resident && have_prev;
+    // lm_frontiers across a failed step: a run that decodes new blobs rebuilds the DAG tables, and a document it fails for has none
+    // afterwards — the heads every document has NOW (the previous run's tables, still in place) are computed unless a call already
+    // did, and kept below for the documents this run fails for.  A run that only moves the rendered versions pays nothing.
+    std::vector<std::vector<uint8_t>> heads_before[2];
+    bool heads_before_ok = false;
+    if (!resident || !have_prev) { heads_kept_on.assign(n_docs, 0); heads_kept[0].assign(n_docs, {}); heads_kept[1].assign(n_docs, {}); }
+    else if (!reuse) {
+      if (!heads_ok) heads_compute();
+      heads_before[0] = h_heads[0]; heads_before[1] = h_heads[1];
+      heads_before_ok = heads_before[0].size() == n_docs && heads_before[1].size() == n_docs;
+    }
     if (resident && have_prev) {
       // the version every document was at before this run (k_import_lca: LCA + DiffMode of the import, dag.rs:487-765): the
       // previous run's document records, peers and applied ends, copied before this run's kernels rebuild the tables.  For a
@@ -1654,6 +1679,9 @@ struct Engine {
           // … and the version it stays at is kept for k_import_lca: what the previous run left (this run's copy of it), or
           // what is kept already when that run had failed too; nothing (the empty version) when no run went through yet
           if (!keep_on[i]) {
+            // (its heads: the previous run's; the empty version — the byte 00 — when no run went through yet; unknown after a run that only moved versions)
+            heads_kept_on[i] = 1;
+            for (int w = 0; w < 2; w++) heads_kept[w][i] = heads_before_ok ? heads_before[w][i] : !have_prev ? std::vector<uint8_t>(1, 0) : std::vector<uint8_t>();
             keep_on[i] = 1; keep_ver[i].clear();
             DocMeta pm;
             if (prev_copied) {
@@ -1666,7 +1694,7 @@ struct Engine {
               }
             }
           }
-        } else { tk_reset[i] = 0; keep_on[i] = 0; }
+        } else { tk_reset[i] = 0; keep_on[i] = 0; heads_kept_on[i] = 0; }
         r_step[i] = 0;
       }
       h_lca.resize((size_t)n_docs * LCA_OUT);
@@ -1679,6 +1707,8 @@ struct Engine {
     ran = true;
     fetched = false;
     last_d = d;
+    last_g = g;
+    ver_peers_ok = false; heads_ok = false;
     rt_ran = false;
   }
 
@@ -1868,6 +1898,141 @@ struct Engine {
     lmbe::flush_times(t);
     for (auto& kt : t) cur_ms += kt.ms;
     for (size_t k = 0; k < idx.size(); k++) out[idx[k]] = r[k];
+  }
+
+  // ---- lm_frontiers / lm_versions (lm_k_version.h): Frontiers <-> VersionVector, heads, comparisons over the applied history, from the
+  // tables the DAG stage of the last run left (last_d, last_g).  The context has parsed the query bytes into (PeerID, counter) rows —
+  // a VersionVector as the last id of every entry above 0; here the queries are grouped by document, launched one wave each and the
+  // answers turned into postcard bytes with the documents' PeerIDs (fetched once per run).
+  struct VersionIn {
+    uint32_t doc; int32_t op;
+    std::vector<std::pair<uint64_t, int64_t>> a, b;   // (PeerID, counter) rows of the two inputs
+  };
+  struct VersionOut { int32_t status = ST_OK; int32_t order = 0; std::vector<uint8_t> bytes; };
+  // the verdict a document gives without a launch: its import error, LM_UNSUPPORTED for one without a rendering
+  int32_t version_doc_status(uint32_t doc) const {
+    const DocMeta& m = h_doc[doc];
+    if (m.status != ST_OK) return m.status;
+    if (m.n_peers > MAX_PEERS) return ST_UNSUPPORTED;
+    return ST_OK;
+  }
+  void version_peers() {
+    if (ver_peers_ok) return;
+    size_t np = 0;
+    for (uint32_t i = 0; i < n_docs && i < h_doc.size(); i++) if (h_doc[i].status == ST_OK) np = std::max(np, (size_t)h_doc[i].praw0 + h_doc[i].n_peers);
+    h_ver_peers.assign(np + 1, 0);
+    if (np) { lmbe::d2h(h_ver_peers.data(), b_peer_uniq.p, np * 8); lmbe::sync(); }
+    ver_peers_ok = true;
+  }
+  static void version_put_uleb(std::vector<uint8_t>& b, uint64_t v) { do { uint8_t x = v & 0x7f; v >>= 7; if (v) x |= 0x80; b.push_back(x); } while (v); }
+  // one launch: qs[k].out0 / a0 / b0 are filled here from `rows_of`; res / words come back per query
+  void version_launch(std::vector<VerQuery>& qs, const std::vector<VerId>& rows, std::vector<VerRes>& res, std::vector<uint32_t>& words) {
+    uint64_t top = 0;
+    for (auto& q : qs) { q.out0 = top; top += 2ull * h_doc[q.doc].n_peers + 2; }
+    const size_t nq = qs.size();
+    b_ver_q.ensure(nq * sizeof(VerQuery)); b_ver_rows.ensure((rows.size() + 1) * sizeof(VerId)); b_ver_res.ensure(nq * sizeof(VerRes)); b_ver_out.ensure((top + 1) * 4);
+    lmbe::h2d(b_ver_q.p, qs.data(), nq * sizeof(VerQuery));
+    if (!rows.empty()) lmbe::h2d(b_ver_rows.p, rows.data(), rows.size() * sizeof(VerId));
+    Dev d = last_d;
+    DevDag g = last_g;
+    std::vector<KernelTime> t;
+    lmbe::reset_times();
+    lmbe::tic(profiling);
+    LM_LAUNCH(k_version, nq, 64, d, g, (const VerQuery*)b_ver_q.as<VerQuery>(), (const VerId*)b_ver_rows.as<VerId>(), b_ver_res.as<VerRes>(), b_ver_out.as<uint32_t>());
+    lmbe::toc("k_version", t, profiling);
+    res.resize(nq); words.resize(top + 1);
+    lmbe::d2h(res.data(), b_ver_res.p, nq * sizeof(VerRes));
+    if (top) lmbe::d2h(words.data(), b_ver_out.p, top * 4);
+    lmbe::sync();
+    lmbe::flush_times(t);
+    for (auto& kt : t) ver_ms += kt.ms;
+  }
+  // Frontiers::encode(): postcard Vec<ID>, (peer index, counter) pairs in ascending peer order
+  void version_frontiers_bytes(const DocMeta& m, const uint32_t* w, uint32_t n, std::vector<uint8_t>& out) const {
+    out.clear();
+    version_put_uleb(out, n);
+    for (uint32_t k = 0; k < n; k++) { version_put_uleb(out, h_ver_peers[m.praw0 + w[2 * k]]); version_put_uleb(out, (uint64_t)w[2 * k + 1] << 1); }
+  }
+  void versions(const std::vector<VersionIn>& in, std::vector<VersionOut>& out) {
+    lmbe::bind(sc);
+    if (!ran) throw std::runtime_error("lm_versions before lm_run");
+    if (shared_mode != 0) throw std::runtime_error("lm_versions: a folded batch has to be unfolded first");
+    out.assign(in.size(), VersionOut());
+    ver_ms = 0;
+    std::vector<uint32_t> idx;
+    for (size_t k = 0; k < in.size(); k++) {
+      if (in[k].doc >= n_docs) throw std::runtime_error("lm_versions: no such document");
+      if (in[k].op < VER_TO_VV || in[k].op > VER_CMP_DOC) throw std::runtime_error("lm_versions: op is one of LM_VER_*");
+      const int32_t st = version_doc_status(in[k].doc);
+      if (st != ST_OK) out[k].status = st; else idx.push_back((uint32_t)k);
+    }
+    if (idx.empty()) return;
+    // by document: the waves of one document run side by side over the same rows of vvh
+    if (!std::is_sorted(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return in[a].doc < in[b].doc; }))
+      std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return in[a].doc < in[b].doc; });
+    std::vector<VerQuery> qs(idx.size());
+    std::vector<VerId> rows;
+    auto put = [&](const std::vector<std::pair<uint64_t, int64_t>>& ids, uint32_t& r0, uint32_t& rn) {
+      r0 = (uint32_t)rows.size(); rn = (uint32_t)ids.size();
+      for (auto& id : ids) rows.push_back(VerId{id.first, id.second < 0 ? 0u : (uint32_t)id.second, id.second < 0 ? 1u : 0u});
+    };
+    for (size_t k = 0; k < idx.size(); k++) {
+      const VersionIn& q = in[idx[k]];
+      memset(&qs[k], 0, sizeof(VerQuery));
+      qs[k].doc = q.doc; qs[k].op = q.op;
+      put(q.a, qs[k].a0, qs[k].na);
+      put(q.b, qs[k].b0, qs[k].nb);
+    }
+    std::vector<VerRes> res;
+    std::vector<uint32_t> words;
+    version_launch(qs, rows, res, words);
+    version_peers();
+    for (size_t k = 0; k < idx.size(); k++) {
+      VersionOut& o = out[idx[k]];
+      const DocMeta& m = h_doc[qs[k].doc];
+      const uint32_t* w = words.data() + qs[k].out0;
+      o.status = res[k].status; o.order = res[k].order;
+      if (o.status != ST_OK) { o.order = 0; continue; }
+      if (qs[k].op == VER_TO_VV) {          // VersionVector::encode(): the peers with a counter above 0, ascending — lm_fetch's bytes
+        uint32_t cnt = 0;
+        for (uint32_t p = 0; p < res[k].n; p++) cnt += w[p] != 0;
+        version_put_uleb(o.bytes, cnt);
+        for (uint32_t p = 0; p < res[k].n; p++) if (w[p]) { version_put_uleb(o.bytes, h_ver_peers[m.praw0 + p]); version_put_uleb(o.bytes, (uint64_t)w[p] << 1); }
+      } else if (qs[k].op == VER_TO_FRONTIERS || qs[k].op == VER_MINIMIZE) version_frontiers_bytes(m, w, res[k].n, o.bytes);
+    }
+  }
+  // lm_frontiers: which = 0 the heads of everything applied, 1 of the version the run rendered; false = unknown (a failed document)
+  bool frontiers(uint32_t doc, int which, std::vector<uint8_t>& out) {
+    lmbe::bind(sc);
+    if (!ran) throw std::runtime_error("lm_frontiers before lm_run");
+    if (shared_mode != 0) throw std::runtime_error("lm_frontiers: a folded batch has to be unfolded first");
+    if (doc >= n_docs) throw std::runtime_error("lm_frontiers: no such document");
+    if (resident && version_doc_status(doc) != ST_OK && doc < heads_kept_on.size() && heads_kept_on[doc]) {   // its last step(s) failed: where it stood before
+      out = heads_kept[which ? 1 : 0][doc];
+      return !out.empty();
+    }
+    if (!heads_ok) heads_compute();
+    out = h_heads[which ? 1 : 0][doc];
+    return !out.empty();
+  }
+  // one launch for every document and both versions, kept until the next run
+  void heads_compute() {
+    ver_ms = 0;
+    h_heads[0].assign(n_docs, {}); h_heads[1].assign(n_docs, {});
+    std::vector<VerQuery> qs;
+    for (uint32_t i = 0; i < n_docs; i++) {
+      if (version_doc_status(i) != ST_OK) continue;
+      for (uint32_t w = 0; w < 2; w++) { VerQuery q; memset(&q, 0, sizeof q); q.doc = i; q.op = VER_HEADS; q.b0 = w; qs.push_back(q); }
+    }
+    if (!qs.empty()) {
+      std::vector<VerRes> res;
+      std::vector<uint32_t> words;
+      version_launch(qs, {}, res, words);
+      version_peers();
+      for (size_t k = 0; k < qs.size(); k++)
+        if (res[k].status == ST_OK) version_frontiers_bytes(h_doc[qs[k].doc], words.data() + qs[k].out0, res[k].n, h_heads[qs[k].b0][qs[k].doc]);
+    }
+    heads_ok = true;
   }
 
   // ---- lm_delta, lm_delta_map, lm_delta_movable (lm_k_delta.h, lm_k_delta_map.h, lm_k_delta_movable.h): what changed from a version A
